@@ -16,6 +16,14 @@ the step (`ms_per_step` = cycle wall-clock).  One step = one pipeline
 Launch (driver): python -m torch.distributed.run --nnodes=1
   --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 Rank 0 prints ONE JSON line; `value` is whole-job rows/sec scored.
+
+A plain run sets up, warms up, times `--steps` cycles and prints the
+line.  `--dump-outputs DIR` additionally writes what the last timed cycle
+computed as `DIR/<name>.npy` (inputs are seeded by date and rank, so two
+builds run with the same arguments can be compared array for array; the
+fp64 reductions use atomics, so metrics and fitted coefficients agree to
+rounding, ~1e-13 relative, not bit for bit).  `--full` is where secondary
+measurements belong; there are none at present.
 """
 from __future__ import annotations
 
@@ -28,6 +36,50 @@ from datetime import date
 from time import perf_counter
 
 import torch
+
+
+DUMP_SAMPLE = 1 << 20  # elements kept per large array (4 MiB as float32)
+METRIC_KEYS = ("MAPE", "r_squared", "max_residual")
+
+
+def _dump_outputs(out_dir: str, result: dict, captured: dict) -> None:
+    """Write what the last timed cycle computed as ``out_dir/<name>.npy``.
+
+    ``X``/``labels`` are stage 3's day-t+1 rows, ``scores`` the deployed
+    scorer's predictions for them, ``model_params`` the stage-1 fit and
+    ``*_metrics`` the fused MAPE / r_squared / max_residual reductions
+    (wall-clock fields are left out: they differ from run to run).  Arrays
+    longer than DUMP_SAMPLE are written as a fixed seeded sample — the same
+    indices for the three per-row arrays — so the dump stays a few MiB
+    at any --rows."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+
+    def sample(t: torch.Tensor) -> "np.ndarray":
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).integers(
+                0, flat.numel(), size=DUMP_SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        return flat.float().cpu().numpy()
+
+    for name in ("X", "labels", "scores"):
+        np.save(os.path.join(out_dir, f"{name}.npy"), sample(captured[name]))
+    for name, metrics in (("online_metrics", result["online"]),
+                          ("offline_metrics", result["offline"])):
+        np.save(os.path.join(out_dir, f"{name}.npy"),
+                np.array([metrics[k] for k in METRIC_KEYS], dtype=np.float64))
+    model = captured.get("model")
+    if hasattr(model, "intercept_"):  # linear: [intercept, coef]
+        params = np.array([model.intercept_, model.coef_], dtype=np.float64)
+    elif hasattr(model, "coef_t_"):  # polynomial ridge, normalised basis
+        params = np.asarray(model.coef_t_, dtype=np.float64)
+    elif model is not None:  # MLP: small vectors whole, W2 sampled
+        params = np.concatenate([sample(t) for t in model.parameters()])
+    else:
+        return
+    np.save(os.path.join(out_dir, "model_params.npy"), params)
 
 
 def main() -> None:
@@ -62,7 +114,17 @@ def main() -> None:
                    help="training window in days, or 'all' for the "
                         "reference's read-all-accumulated-data semantics "
                         "(stage_1:59-71; history grows by --rows each step)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "step computed (rank 0's shard) to DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements; a plain run "
+                        "does only what the headline figure needs (there "
+                        "are none at present: other models, sizes and "
+                        "serving modes are runs of their own)")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
     history_days = None if args.history == "all" else int(args.history)
 
     # mlp-fp8: the MLP with MX-fp8 scoring forward (K=128 scaled MFMA,
@@ -110,13 +172,15 @@ def main() -> None:
     from bodywork_mlops_demo_amd.pipeline.cycle import CycleState, run_cycle
     from bodywork_mlops_demo_amd.store import LocalStore
 
-    # shared store dir across ranks
+    # shared store dir across ranks; the default is per user (another
+    # user's leftover dir could not be cleared) and is removed at exit
     if args.store:
         store_dir = args.store
     else:
         store_dir = os.path.join(
             tempfile.gettempdir(),
-            f"bodywork_bench_{os.environ.get('MASTER_PORT', 'solo')}",
+            f"bodywork_bench_{os.getuid()}_"
+            f"{os.environ.get('MASTER_PORT', 'solo')}",
         )
     if rank == 0:
         shutil.rmtree(store_dir, ignore_errors=True)
@@ -129,7 +193,7 @@ def main() -> None:
                        history_days=history_days)
     scorer_cache: dict = {}
 
-    def one_cycle():
+    def one_cycle(capture=None):
         return run_cycle(
             state, store, args.rows, model_type=args.model,
             process_group=pg, persist_fmt="npy",
@@ -137,6 +201,7 @@ def main() -> None:
             use_graphs=not args.no_graphs and use_cuda,
             scorer_cache=scorer_cache,
             serving=args.serving, http_mode=args.http_mode,
+            capture=capture,
         )
 
     def barrier_sync():
@@ -152,8 +217,11 @@ def main() -> None:
     t0 = perf_counter()
     rows_scored = 0
     last = None
-    for _ in range(args.steps):
-        last = one_cycle()
+    # the last timed step hands out references to its tensors (no copies,
+    # no extra launches) so --dump-outputs can write them after the clock
+    captured: dict | None = {} if args.dump_outputs and rank == 0 else None
+    for i in range(args.steps):
+        last = one_cycle(captured if i == args.steps - 1 else None)
         rows_scored += last["timings"]["rows_scored"]
     state.drain_io()  # async artefact writes are part of the timed work
     barrier_sync()
@@ -174,6 +242,9 @@ def main() -> None:
     replica = scorer_cache.get("http_replica")
     if replica is not None:
         replica.stop()
+
+    if captured is not None:
+        _dump_outputs(args.dump_outputs, last, captured)
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1000.0
@@ -228,6 +299,8 @@ def main() -> None:
     if pg is not None:
         torch.distributed.barrier(pg)
         torch.distributed.destroy_process_group()
+    if rank == 0 and not args.store:
+        shutil.rmtree(store_dir, ignore_errors=True)
 
 
 if __name__ == "__main__":

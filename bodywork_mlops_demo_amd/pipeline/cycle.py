@@ -249,6 +249,7 @@ def run_cycle(
     serving: str = "inprocess",
     http_mode: str = "binary",
     http_port: int = 5600,
+    capture: dict | None = None,
 ) -> dict:
     """Run one full cycle; returns per-phase timings + metrics.
 
@@ -265,6 +266,10 @@ def run_cycle(
     meaning; ``"inprocess"`` scores through the resident BatchedScorer
     (no HTTP inside the timed region — the faster hermetic path, whose
     per-row time is persisted as kind ``amortised-gpu-batch``).
+
+    ``capture``, when given, receives references to what this cycle
+    computed beyond the returned metrics: the trained ``model`` and the
+    day-t+1 ``X``/``labels``/``scores`` tensors of stage 4.
     """
     device = state.device
     dev_cuda = device.startswith("cuda")
@@ -301,10 +306,11 @@ def run_cycle(
             replica = scorer_cache["http_replica"]
             return _finish_cycle(state, store, n_rows, persist_fmt, None,
                                  timings, metrics, sync,
-                                 http=(replica.url, http_mode))
+                                 http=(replica.url, http_mode),
+                                 capture=capture)
         scorer = scorer_cache["scorer"]
         return _finish_cycle(state, store, n_rows, persist_fmt, scorer,
-                             timings, metrics, sync)
+                             timings, metrics, sync, capture=capture)
     metrics, trained = stage1.run(
         eff_store,
         model_type=model_type,
@@ -320,6 +326,8 @@ def run_cycle(
     )
     sync()
     timings["train_s"] = perf_counter() - t0
+    if capture is not None:
+        capture["model"] = trained
 
     # -- stage 2: deploy — joblib artefact round-trip, model into HBM,
     #    hipGraphs captured (reference stage_2:108-119 semantics) ----------
@@ -354,7 +362,7 @@ def run_cycle(
         timings["deploy_s"] = perf_counter() - t0
         return _finish_cycle(state, store, n_rows, persist_fmt, None,
                              timings, metrics, sync,
-                             http=(replica.url, http_mode))
+                             http=(replica.url, http_mode), capture=capture)
     if store is not None:
         if process_group is not None:  # rank 0 persisted; others wait
             import torch.distributed as dist
@@ -391,11 +399,12 @@ def run_cycle(
     timings["deploy_s"] = perf_counter() - t0
 
     return _finish_cycle(state, store, n_rows, persist_fmt, scorer, timings,
-                         metrics, sync)
+                         metrics, sync, capture=capture)
 
 
 def _finish_cycle(state, store, n_rows, persist_fmt, scorer, timings,
-                  metrics, sync, http: tuple[str, str] | None = None):
+                  metrics, sync, http: tuple[str, str] | None = None,
+                  capture: dict | None = None):
     """Stages 3+4 and clock advance (shared by train and skip-train paths).
 
     ``http=(url, mode)`` routes stage 4 over the wire to a live replica
@@ -424,6 +433,7 @@ def _finish_cycle(state, store, n_rows, persist_fmt, scorer, timings,
             url=url, mode=mode, device=device,
             data=(y_next, X_next, next_date),
             persist=store is not None and state.rank == 0,
+            capture=capture,
         )
     else:
         test_metrics = stage4.run(
@@ -432,6 +442,7 @@ def _finish_cycle(state, store, n_rows, persist_fmt, scorer, timings,
             scorer=scorer,
             data=(y_next, X_next, next_date),
             persist=store is not None and state.rank == 0,
+            capture=capture,
         )
     sync()
     timings["test_s"] = perf_counter() - t0

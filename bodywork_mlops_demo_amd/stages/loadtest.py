@@ -149,12 +149,15 @@ def run(
     scorer=None,
     data: tuple[torch.Tensor, torch.Tensor, date_t] | None = None,
     persist: bool = True,
+    capture: dict | None = None,
 ) -> dict:
     """Score the latest dataset against the service; persist test metrics.
 
     ``scorer`` bypasses HTTP entirely (in-process serving replica) for the
     hermetic pipeline/bench path; ``data`` skips the store read when the
-    tensors are already device-resident.
+    tensors are already device-resident.  ``capture``, when given, receives
+    references to the tensors the metrics were computed from (``X``,
+    ``labels``, ``scores``) — no extra work, the caller just gets to see them.
     """
     device = device or ("cuda" if torch.cuda.is_available() else "cpu")
     if data is None:
@@ -193,6 +196,8 @@ def run(
 
     scores = scores.to(device)
     labels = labels.to(device)
+    if capture is not None:
+        capture.update(X=X, labels=labels, scores=scores)
     metrics = ops.score_label_metrics(scores, labels)
     metrics["mean_response_time"] = mean_rt
     metrics["response_time_kind"] = rt_kind

@@ -45,17 +45,26 @@ def _param_tensors(model) -> list[torch.Tensor]:
 
 def check_model(model_type: str, args, device: str, rank: int, world: int,
                 pg) -> float:
-    from bodywork_mlops_demo_amd.pipeline.cycle import CycleState, run_cycle
     from bodywork_mlops_demo_amd.store import LocalStore
 
-    store_dir = os.path.join(
-        tempfile.gettempdir(),
-        f"dist_parity_{os.environ.get('MASTER_PORT', '0')}_{model_type}")
+    # rank 0 makes a fresh private store dir and tells the others; a fixed
+    # name under the shared temp dir breaks as soon as another user's run
+    # has left one behind (it can be neither cleared nor written)
+    shared = [tempfile.mkdtemp(prefix=f"dist_parity_{model_type}_")
+              if rank == 0 else None]
+    dist.broadcast_object_list(shared, src=0, group=pg)
+    store_dir = shared[0]
+    store = LocalStore(store_dir)
+    max_diff = _check_model(model_type, args, device, rank, world, pg, store)
+    dist.barrier(group=pg)
     if rank == 0:
         shutil.rmtree(store_dir, ignore_errors=True)
-        os.makedirs(store_dir, exist_ok=True)
-    dist.barrier(group=pg)
-    store = LocalStore(store_dir)
+    return max_diff
+
+
+def _check_model(model_type: str, args, device: str, rank: int, world: int,
+                 pg, store) -> float:
+    from bodywork_mlops_demo_amd.pipeline.cycle import CycleState, run_cycle
 
     state = CycleState(device, date(2026, 2, 1), rank=rank, world_size=world,
                        history_days=1)
