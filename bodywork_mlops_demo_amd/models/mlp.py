@@ -14,6 +14,9 @@ K=1 MFMA launch would waste the matrix cores — MI355X-first design).
 Training: minibatch Adam on MSE; forward/backward matmuls are the
 hand-written bf16 MFMA kernels (fp32 accumulate), optimizer state fp32.
 In DP training gradients are bucket-all-reduced over RCCL.
+Opt-in (``fp8_training=True`` / ``BODYWORK_MLP_FP8_TRAIN=1``): the
+training forward's h2 GEMM runs on MX-fp8 (e4m3) operands with
+per-fit static exponents; the backward is unchanged.
 
 Artefact: a *real sklearn ``MLPRegressor``* with ``coefs_``/``intercepts_``
 injected, so ``joblib.load`` + ``predict`` work with stock sklearn
@@ -42,8 +45,13 @@ class GPUMLPRegressor:
     X_MU = 50.0
     X_SIGMA = 28.86751345948129
 
+    #: data-free bound on |xn| for the reference's X ~ U(0,100)
+    #: (stage_3:39): (100 - mu) / sigma ~= 1.74
+    XN_BOUND = 1.8
+
     def __init__(self, hidden: int = 4096, device="cpu", seed: int = 7,
-                 fp8_scoring: bool | None = None):
+                 fp8_scoring: bool | None = None,
+                 fp8_training: bool | None = None):
         self.hidden = hidden
         self.device = canonical_device(device)
         # opt-in MX-fp8 scoring forward (2x-rate K=128 scaled MFMA for the
@@ -57,6 +65,17 @@ class GPUMLPRegressor:
         self._w2_q8: torch.Tensor | None = None
         self._e_w2: int | None = None
         self._e_h1: int | None = None
+        # opt-in MX-fp8 TRAINING forward: the h2 = relu(h1 @ W2 + b2) GEMM
+        # runs on e4m3 operands (the two backward GEMMs stay bf16 and the
+        # gradients pass straight through the quantisation).  Its shadow
+        # and exponents are separate from the scoring ones above.
+        if fp8_training is None:
+            import os as _os
+
+            fp8_training = _os.environ.get("BODYWORK_MLP_FP8_TRAIN",
+                                           "0") == "1"
+        self.fp8_training = fp8_training
+        self._init_fp8_train_state()
         g = torch.Generator(device="cpu").manual_seed(seed)
         h = hidden
         # He init, fp32 master weights
@@ -75,6 +94,7 @@ class GPUMLPRegressor:
         for name in ("w1", "b1", "W2", "b2", "w3", "b3"):
             setattr(self, name, getattr(self, name).to(d))
         self._w2_q8 = None  # fp8 shadow re-created lazily on new device
+        self._w2_q8_tr = None
         self._refresh_bf16()
 
     def _refresh_bf16(self):
@@ -104,6 +124,7 @@ class GPUMLPRegressor:
         for name in ("w1_bf", "b1_bf", "W2w_bf", "W2wt_bf", "b2_bf", "w3_bf"):
             getattr(self, name).copy_(getattr(other, name).to(self.device))
         self._refresh_fp8()
+        self._refresh_fp8_train()
         return True
 
     # -- MX-fp8 scoring shadows -------------------------------------------
@@ -132,6 +153,75 @@ class GPUMLPRegressor:
                 + self.b1.abs().max().item()
             self._e_h1 = ops.e4m3_exponent(bound)
 
+    # -- MX-fp8 training shadow ------------------------------------------
+    def _init_fp8_train_state(self) -> None:
+        self._w2_q8_tr: torch.Tensor | None = None
+        self._e_w2_tr: int | None = None
+        self._e_h1_tr: int | None = None
+        self._xn_max_tr: float = self.XN_BOUND
+
+    def _fp8_train_exponents(self, xn_max: float, lr: float = 0.0,
+                             steps: int = 0) -> tuple[int, int]:
+        """(e_w2, e_h1) valid for a whole ``fit`` of ``steps`` Adam steps.
+
+        Adam moves every weight by at most lr*(1-b1)/sqrt(1-b2) = 3.16*lr
+        per step for betas (0.9, 0.999), so ``d = 3.2*lr*steps`` bounds
+        the total drift of any element and the exponents can stay STATIC
+        (baked into the captured step graph) without saturating.  e4m3 is
+        a floating format: the headroom only raises the subnormal floor,
+        it costs no relative precision."""
+        d = 3.2 * lr * steps
+        w2 = self.W2.abs().max().item() + d
+        h1 = (xn_max * (self.w1.abs().max().item() + d)
+              + self.b1.abs().max().item() + d)
+        return ops.e4m3_exponent(w2), ops.e4m3_exponent(h1)
+
+    def _prepare_fp8_training(self, X: torch.Tensor | None = None,
+                              lr: float = 0.0, steps: int = 0) -> None:
+        """Fix the training exponents (from this fit's data and update
+        budget) and quantise the W2 shadow.  Host-syncing — must run
+        before any graph capture.  The shadow tensor is persistent:
+        later refreshes requantise into it in place."""
+        if X is not None and X.numel() > 0:
+            xn = (X.float() - self.X_MU) / self.X_SIGMA
+            self._xn_max_tr = xn.abs().max().item()
+        self._e_w2_tr, self._e_h1_tr = self._fp8_train_exponents(
+            self._xn_max_tr, lr, steps)
+        if self._w2_q8_tr is None:
+            self._w2_q8_tr = ops.quantize_e4m3(self.W2w_bf, self._e_w2_tr)
+        else:
+            self._refresh_fp8_train()
+
+    def _refresh_fp8_train(self) -> None:
+        """Requantise the training W2 shadow IN PLACE from ``W2w_bf``
+        (after every weight update; graph-safe: tensor in, ``copy_`` into
+        the persistent tensor, int exponent baked)."""
+        if self._w2_q8_tr is None:
+            return
+        self._w2_q8_tr.copy_(ops.quantize_e4m3(self.W2w_bf, self._e_w2_tr))
+
+    def _fp8_train_saturated(self) -> list[str]:
+        """Names of the tensors whose current range exceeds what the
+        training exponents represent without saturation (empty = ok)."""
+        if self._e_w2_tr is None:
+            return []
+        bad = []
+        if self.W2.abs().max().item() > 448.0 * 2.0 ** self._e_w2_tr:
+            bad.append("W2")
+        h1 = (self._xn_max_tr * self.w1.abs().max().item()
+              + self.b1.abs().max().item())
+        if h1 > 448.0 * 2.0 ** self._e_h1_tr:
+            bad.append("h1")
+        return bad
+
+    def _use_fp8_train(self, m: int) -> bool:
+        """MX-fp8 training forward is opt-in and, on GPU, tile-shape-gated
+        like the scoring path; on CPU the oracles serve any shape."""
+        if not self.fp8_training:
+            return False
+        return (self.device.type != "cuda"
+                or (m % 256 == 0 and self.hidden % 256 == 0))
+
     def parameters(self) -> list[torch.Tensor]:
         return [self.w1, self.b1, self.W2, self.b2, self.w3, self.b3]
 
@@ -141,7 +231,18 @@ class GPUMLPRegressor:
         their 1-bit activation masks (consumed by the masked backward —
         16x less mask traffic than re-reading the activations)."""
         xn = (x.float() - self.X_MU) / self.X_SIGMA
-        if want_masks:
+        if want_masks and self._use_fp8_train(xn.shape[0]):
+            # fp8 training forward: dual-emit layer 1 (bf16 + mask for the
+            # backward, e4m3 for the GEMM) and the 2x-rate MX GEMM with
+            # the mask-emitting epilogue; backward is unchanged
+            if self._w2_q8_tr is None:
+                self._prepare_fp8_training()
+            h1, m1, h1q = ops.expand1d_bf16_e4m3(xn, self.w1_bf, self.b1_bf,
+                                                 self._e_h1_tr)
+            h2, m2 = ops.gemm_mx8_relu_mask(h1q, self._e_h1_tr,
+                                            self._w2_q8_tr, self._e_w2_tr,
+                                            self.b2)
+        elif want_masks:
             h1, m1 = ops.expand1d_bf16(xn, self.w1_bf, self.b1_bf, relu=True,
                                        emit_mask=True)
             h2, m2 = ops.linear_relu_mask_bf16(h1, self.W2w_bf, self.b2_bf)
@@ -221,6 +322,18 @@ class GPUMLPRegressor:
         """Minibatch Adam on MSE.  With ``process_group``, each rank holds
         a shard of (X, y); gradients are all-reduce-averaged per step
         (flat fp32 bucket — one RCCL launch per step)."""
+        if self.fp8_training:
+            # static exponents for the whole fit, fixed before any capture
+            self._prepare_fp8_training(X.to(self.device), lr, steps)
+        self._fit_loop(X, y, steps, batch_size, lr, process_group, seed)
+        if self.fp8_training:
+            for name in self._fp8_train_saturated():
+                log.warning(
+                    f"fp8 training: {name} outgrew its static e4m3 exponent "
+                    "during fit (values saturate at 448*2^e)")
+        return self
+
+    def _fit_loop(self, X, y, steps, batch_size, lr, process_group, seed):
         n = X.shape[0]
         g = torch.Generator(device="cpu").manual_seed(seed)
         if self._opt_state is None:
@@ -253,7 +366,7 @@ class GPUMLPRegressor:
                 self._fit_captured(X.to(self.device), y.to(self.device),
                                    steps, min(batch_size, n), lr, seed,
                                    process_group)
-                return self
+                return
             except RuntimeError:
                 if process_group is None:
                     raise
@@ -280,7 +393,6 @@ class GPUMLPRegressor:
                     off += gr.numel()
             t += 1
             self._adam_update(grads, lr, t)
-        return self
 
     def reinit_(self, seed: int = 7) -> "GPUMLPRegressor":
         """Re-randomise weights and reset optimiser state IN PLACE, so a
@@ -313,6 +425,7 @@ class GPUMLPRegressor:
         self.b2_bf.copy_(self.b2.bfloat16())
         self.w3_bf.copy_(self.w3.bfloat16())
         self._refresh_fp8()
+        self._refresh_fp8_train()
         return self
 
     def _fit_captured(self, X, y, steps: int, bs: int, lr: float, seed: int,
@@ -330,8 +443,13 @@ class GPUMLPRegressor:
 
             world = dist.get_world_size(process_group)
         st = getattr(self, "_train_static", None)
+        # the fp8 exponents are baked into kernel arguments at capture:
+        # a change in the flag or either exponent needs a new graph
+        fp8_key = ((True, self._e_w2_tr, self._e_h1_tr)
+                   if self.fp8_training else (False, None, None))
         if (st is None or st["cap"] < n or st["bs"] != bs or st["lr"] != lr
-                or st.get("world", 1) != world):
+                or st.get("world", 1) != world
+                or st.get("fp8_key") != fp8_key):
             cap = max(n, int(st["cap"]) if st else 0)
             st = {
                 "cap": cap, "bs": bs, "lr": lr,
@@ -340,7 +458,7 @@ class GPUMLPRegressor:
                 "n_dev": torch.zeros(1, dtype=torch.int64, device=self.device),
                 "ctr": torch.zeros(1, dtype=torch.int64, device=self.device),
                 "bc": torch.ones(2, device=self.device),
-                "graph": None, "world": world,
+                "graph": None, "world": world, "fp8_key": fp8_key,
             }
             self._train_static = st
         st["X"][:n].copy_(X)
@@ -374,6 +492,7 @@ class GPUMLPRegressor:
                 ops.adam_step(p, gr, m, v, sh, lr, t=1, bc=bc)
             # refresh the transposed forward copy in place (graph-safe)
             self.W2w_bf.copy_(ops.transpose_bf16(self.W2wt_bf))
+            self._refresh_fp8_train()
 
         t0 = 1
         if st["graph"] is None:
@@ -386,7 +505,15 @@ class GPUMLPRegressor:
                 one_step()
             torch.cuda.current_stream().wait_stream(stream)
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
+            # With a process group the NCCL watchdog thread polls the
+            # warmup all-reduce's completion event (hipEventQuery) every
+            # ~100 ms.  Under the default GLOBAL capture mode a poll that
+            # lands inside the capture returns a stream-capture error,
+            # which the watchdog rethrows and the process aborts — a
+            # timing race.  thread_local mode restricts the capture's
+            # API checks to this thread (same choice as BatchedScorer).
+            mode = "thread_local" if process_group is not None else "global"
+            with torch.cuda.graph(graph, capture_error_mode=mode):
                 one_step()
             st["graph"] = graph
             t0 = 2  # the warmup was step 1
@@ -424,10 +551,12 @@ class GPUMLPRegressor:
                                         self._opt_state, shadows):
                 ops.adam_step(p, gr, m, v, s, lr, t, beta1, beta2, eps)
             self.W2w_bf = ops.transpose_to_bf16(self.W2)
+            self._refresh_fp8_train()
             return
         for p, gr, (m, v) in zip(self.parameters(), grads, self._opt_state):
             ops.adam_step(p, gr, m, v, None, lr, t, beta1, beta2, eps)
         self._refresh_bf16()
+        self._refresh_fp8_train()
 
     # -- artefact compatibility --------------------------------------------
     def to_sklearn(self):
@@ -480,6 +609,9 @@ class GPUMLPRegressor:
         self._w2_q8 = None
         self._e_w2 = None
         self._e_h1 = None
+        self.fp8_training = _os.environ.get("BODYWORK_MLP_FP8_TRAIN",
+                                            "0") == "1"
+        self._init_fp8_train_state()
         self._to_device()
         return self
 

@@ -488,6 +488,53 @@ def gemm_mx8_relu_dot(
     return h2 @ w3.float()
 
 
+def gemm_mx8_relu_mask(
+    a8: torch.Tensor,
+    ea: int,
+    b8: torch.Tensor,
+    eb: int,
+    bias: torch.Tensor | None = None,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """relu(2^(ea+eb)·(a8·b8ᵀ) + bias) as bf16 AND its 1-bit activation
+    mask (uint8 [M, N/8]) in one pass — the MX-fp8 twin of
+    :func:`linear_relu_mask_bf16` for the opt-in fp8 training forward.
+
+    The mask tests the fp32 epilogue value (strict ``> 0``); the bf16
+    output is bit-identical to ``gemm_mx8_nt(..., relu=True)``.  ``bias``
+    is fp32 [N].  Requires M%256==0, N%256==0, K%128==0 on GPU.
+    CPU oracle: decode + fp32 matmul + pack_relu_mask.
+    """
+    if a8.device.type == "cuda":
+        core = _core(a8.device)
+        return core.gemm_mx8_relu_mask(
+            a8.contiguous(), int(ea), b8.contiguous(), int(eb),
+            bias.contiguous().float() if bias is not None else None)
+    c = reference.gemm_mx8_nt_cpu(a8, ea, b8, eb, bias, relu=True,
+                                  out_fp32=True)
+    return c.to(torch.bfloat16), reference.pack_relu_mask(c > 0)
+
+
+def expand1d_bf16_e4m3(
+    x: torch.Tensor,
+    w: torch.Tensor,
+    b: torch.Tensor | None,
+    e: int,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """h = relu(x*w + b) emitted in ONE pass as (bf16 activation, 1-bit
+    mask, e4m3 bytes with value = 2^e * stored) — the fp8 training
+    forward's layer 1: the backward needs the bf16 copy and the mask, the
+    MX GEMM needs the e4m3 copy.  Each output is bit-identical to the
+    single-output op (``expand1d_bf16(relu=True, emit_mask=True)`` /
+    ``expand1d_e4m3``).  CPU oracle: composition of those two ops."""
+    if x.device.type == "cuda":
+        core = _core(x.device)
+        return core.expand1d_bf16_e4m3(
+            x.contiguous().float(), w.contiguous(),
+            b.contiguous() if b is not None else None, int(e))
+    h, mask = reference.expand1d_cpu(x, w, b, relu=True, emit_mask=True)
+    return h, mask, expand1d_e4m3(x, w, b, e)
+
+
 def linear_relu_dot_bf16(
     x: torch.Tensor,
     w: torch.Tensor,

@@ -55,6 +55,12 @@ at::Tensor gemm_mx8_nt_hip(const at::Tensor& a8, int64_t ea,
 at::Tensor gemm_mx8_relu_dot_hip(const at::Tensor& a8, int64_t ea,
                                  const at::Tensor& b8, int64_t eb,
                                  const at::Tensor& b2, const at::Tensor& w3);
+std::tuple<at::Tensor, at::Tensor, at::Tensor> expand1d_bf16_e4m3_hip(
+    const at::Tensor& x, const at::Tensor& w,
+    const c10::optional<at::Tensor>& b, int64_t e);
+std::tuple<at::Tensor, at::Tensor> gemm_mx8_relu_mask_hip(
+    const at::Tensor& a8, int64_t ea, const at::Tensor& b8, int64_t eb,
+    const c10::optional<at::Tensor>& bias);
 // optim.hip
 void adam_step_hip(at::Tensor p, const at::Tensor& g, at::Tensor m,
                    at::Tensor v, const c10::optional<at::Tensor>& p_bf16,
@@ -92,6 +98,10 @@ TORCH_LIBRARY(bodywork_hip, m) {
         "bool relu, bool out_fp32) -> Tensor");
   m.def("gemm_mx8_relu_dot(Tensor a8, int ea, Tensor b8, int eb, "
         "Tensor b2, Tensor w3) -> Tensor");
+  m.def("expand1d_bf16_e4m3(Tensor x, Tensor w, Tensor? b, int e) -> "
+        "(Tensor, Tensor, Tensor)");
+  m.def("gemm_mx8_relu_mask(Tensor a8, int ea, Tensor b8, int eb, "
+        "Tensor? bias) -> (Tensor, Tensor)");
   m.def("gemm8_relu_dot_bf16(Tensor x, Tensor w, Tensor b2, Tensor w3) "
         "-> Tensor");
   m.def("adam_step(Tensor(a!) p, Tensor g, Tensor(b!) m, Tensor(c!) v, "
@@ -123,6 +133,8 @@ TORCH_LIBRARY_IMPL(bodywork_hip, CUDA, m) {
   m.impl("expand1d_e4m3", expand1d_e4m3_hip);
   m.impl("gemm_mx8_nt", gemm_mx8_nt_hip);
   m.impl("gemm_mx8_relu_dot", gemm_mx8_relu_dot_hip);
+  m.impl("expand1d_bf16_e4m3", expand1d_bf16_e4m3_hip);
+  m.impl("gemm_mx8_relu_mask", gemm_mx8_relu_mask_hip);
   m.impl("gemm8_relu_dot_bf16", gemm8_relu_dot_bf16_hip);
   m.impl("adam_step", adam_step_hip);
   m.impl("batch_indices", batch_indices_hip);

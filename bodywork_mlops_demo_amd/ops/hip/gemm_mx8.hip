@@ -72,12 +72,15 @@ __device__ __forceinline__ void mx_stage_half(char* __restrict__ slot,
   mx_glds16(base + off0, slot + wave * 1024);
 }
 
-template <int EPI, bool HAS_BIAS, bool OUT_FP32>
+// EMIT_MASK: also write the 1-bit ReLU mask of the produced activations
+// (uint8 [M, N/8], bit e of byte c = column 8c+e > 0 — the layout the
+// masked backward consumes, same emit as gemm8.hip's g8_epilogue).
+template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false>
 __device__ __forceinline__ void mx_epilogue(
     mx_f32x4 (&acc)[4][4], const float* __restrict__ bias,
-    const float* __restrict__ w3, void* __restrict__ C, long long M,
-    long long N, long long m0, long long n0, int wm, int wn, int fl,
-    int kg) {
+    const float* __restrict__ w3, unsigned char* __restrict__ mask_out,
+    void* __restrict__ C, long long M, long long N, long long m0,
+    long long n0, int wm, int wn, int fl, int kg) {
   if (EPI == MX_EPI_RELU_DOT) {
     // fused scoring head: y[row] += sum_col relu(acc + b2[col]) *
     // w3[col] — the h2 activation tensor is never materialised (saves
@@ -129,6 +132,17 @@ __device__ __forceinline__ void mx_epilogue(
           v += bval;
           v = fmaxf(v, 0.0f);
         }
+        if (EMIT_MASK) {
+          // wave-wide ballot OUTSIDE the row/col conditional; lane
+          // kg*16+fl holds (row of kg, col fl), so each kg group's 16-bit
+          // slice is two consecutive mask bytes of its row
+          unsigned long long bal = __ballot(v > 0.0f);
+          if (fl == 0 && row < M && col_ok) {
+            unsigned short bits =
+                (unsigned short)((bal >> (kg * 16)) & 0xFFFF);
+            *(unsigned short*)(mask_out + row * (N >> 3) + (col >> 3)) = bits;
+          }
+        }
         if (row < M && col_ok) {
           if (OUT_FP32)
             ((float*)C)[row * N + col] = v;
@@ -140,13 +154,13 @@ __device__ __forceinline__ void mx_epilogue(
   }
 }
 
-template <int EPI, bool HAS_BIAS, bool OUT_FP32>
+template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false>
 __launch_bounds__(MX_THREADS)
 __global__ void gemm_mx8_nt_kernel(
     const unsigned char* __restrict__ A,  // [M,K] e4m3, row-major
     const unsigned char* __restrict__ B,  // [N,K] e4m3, row-major
     const float* __restrict__ bias, const float* __restrict__ w3,
-    void* __restrict__ C, long long M,
+    unsigned char* __restrict__ mask_out, void* __restrict__ C, long long M,
     long long N, long long K, int sa, int sb,
     int super,      // supertile height in y-blocks (sa/sb: E8M0 bytes)
     int xcd_aware) {
@@ -325,8 +339,8 @@ __global__ void gemm_mx8_nt_kernel(
 #undef MX_ASLOT
 #undef MX_BSLOT
 
-  mx_epilogue<EPI, HAS_BIAS, OUT_FP32>(acc, bias, w3, C, M, N, m0, n0, wm,
-                                       wn, fl, kg);
+  mx_epilogue<EPI, HAS_BIAS, OUT_FP32, EMIT_MASK>(
+      acc, bias, w3, mask_out, C, M, N, m0, n0, wm, wn, fl, kg);
 }
 
 // ---- per-tensor e4m3 quantisation ----------------------------------------
@@ -388,13 +402,13 @@ __global__ void quantize_e4m3_kernel(const T* __restrict__ x,
 #define P1_ASLOT(buf, half) (lds + ((buf) * 2 + (half)) * MX_HTB)
 #define P1_BSLOT(buf, half) (lds + (4 + (buf) * 2 + (half)) * MX_HTB)
 
-template <int EPI, bool HAS_BIAS, bool OUT_FP32>
+template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false>
 __launch_bounds__(MX_THREADS)
 __global__ void gemm_mx8_nt_1p_kernel(
     const unsigned char* __restrict__ A, const unsigned char* __restrict__ B,
     const float* __restrict__ bias, const float* __restrict__ w3,
-    void* __restrict__ C, long long M, long long N, long long K, int sa,
-    int sb) {
+    unsigned char* __restrict__ mask_out, void* __restrict__ C, long long M,
+    long long N, long long K, int sa, int sb) {
   __shared__ char lds[10 * MX_HTB];  // A 2 slots + B 3 slots, 160 KB
   const long long m0 = (long long)blockIdx.y * MX_BM;
   const long long n0 = (long long)blockIdx.x * MX_BN;
@@ -510,8 +524,8 @@ __global__ void gemm_mx8_nt_1p_kernel(
 #undef P1_AR_BASE
 #undef P1_BR_BASE
 
-  mx_epilogue<EPI, HAS_BIAS, OUT_FP32>(acc, bias, w3, C, M, N, m0, n0, wm,
-                                       wn, fl, kg);
+  mx_epilogue<EPI, HAS_BIAS, OUT_FP32, EMIT_MASK>(
+      acc, bias, w3, mask_out, C, M, N, m0, n0, wm, wn, fl, kg);
 }
 
 // ---- fused rank-1 expand -> e4m3 ------------------------------------------
@@ -550,6 +564,52 @@ __global__ void expand1d_e4m3_kernel(const float* __restrict__ x,
       packed |= (unsigned long long)(pk & 0xFFFFu) << (16 * p);
     }
     *(unsigned long long*)(out + row * (long long)h8 * 8 + c8 * 8) = packed;
+  }
+}
+
+// ---- dual-emit rank-1 expand: bf16 + 1-bit mask + e4m3 --------------------
+//
+// The MLP fp8 TRAINING forward's layer 1: h1 = relu(x*w + b) is needed
+// as bf16 (dW2 = h1^T . dz2 in the backward), as its 1-bit mask (masked
+// backward) and as e4m3 (A operand of the MX GEMM).  One pass writes all
+// three from the same fp32 value (3.125 B/element) instead of a separate
+// quantise pass re-reading the bf16 copy (+3 B/element).  Arithmetic is
+// that of expand1d_kernel<relu, emit_mask> and expand1d_e4m3_kernel, so
+// each output is bit-identical to the single-output kernel's.
+template <bool HAS_BIAS>
+__global__ void expand1d_bf16_e4m3_kernel(
+    const float* __restrict__ x, const bf16_t* __restrict__ w,
+    const bf16_t* __restrict__ b, bf16_t* __restrict__ out,
+    unsigned char* __restrict__ mask_out, unsigned char* __restrict__ out8,
+    long long n, int h8 /* H/8 */, float inv_scale) {
+  const long long total = (long long)n * h8;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+       idx < total; idx += stride) {
+    const long long row = idx / h8;
+    const int c8 = (int)(idx % h8);
+    float xv = x[row];
+    float wv[8], bv[8], acc[8];
+    bf16x8_to_f32(load_bf16x8(w + c8 * 8), wv);
+    if (HAS_BIAS) bf16x8_to_f32(load_bf16x8(b + c8 * 8), bv);
+    unsigned char mb = 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      acc[e] = HAS_BIAS ? fmaf(xv, wv[e], bv[e]) : xv * wv[e];
+      acc[e] = fmaxf(acc[e], 0.0f);
+      mb |= (acc[e] > 0.0f ? 1u : 0u) << e;
+    }
+    unsigned long long packed = 0;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      unsigned int pk = (unsigned int)__builtin_amdgcn_cvt_pk_fp8_f32(
+          acc[2 * p] * inv_scale, acc[2 * p + 1] * inv_scale, 0, false);
+      packed |= (unsigned long long)(pk & 0xFFFFu) << (16 * p);
+    }
+    const long long o = row * (long long)h8 * 8 + c8 * 8;
+    mask_out[row * h8 + c8] = mb;
+    store_bf16x8(out + o, f32_to_bf16x8(acc));
+    *(unsigned long long*)(out8 + o) = packed;
   }
 }
 
@@ -621,6 +681,45 @@ at::Tensor expand1d_e4m3_hip(const at::Tensor& x, const at::Tensor& w,
   return out;
 }
 
+std::tuple<at::Tensor, at::Tensor, at::Tensor> expand1d_bf16_e4m3_hip(
+    const at::Tensor& x, const at::Tensor& w,
+    const c10::optional<at::Tensor>& b, int64_t e) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat);
+  TORCH_CHECK(w.scalar_type() == at::kBFloat16);
+  const long long n = x.numel();
+  const long long H = w.numel();
+  TORCH_CHECK(H % 8 == 0, "expand1d_bf16_e4m3: H must be a multiple of 8");
+  const bool has_bias = b.has_value();
+  if (has_bias)
+    TORCH_CHECK(b->scalar_type() == at::kBFloat16 && b->numel() == H,
+                "expand1d_bf16_e4m3: bias must be bf16 [H]");
+  auto out = at::empty({n, H}, w.options());
+  auto mask_out = at::empty({n, H / 8}, w.options().dtype(at::kByte));
+  auto out8 = at::empty({n, H}, w.options().dtype(at::kByte));
+  auto stream = at::cuda::getCurrentCUDAStream();
+  long long total = n * (H / 8);
+  if (total == 0) return {out, mask_out, out8};
+  int grid = (int)std::min<long long>((total + 255) / 256, 2048);
+  float inv_scale = ldexpf(1.0f, (int)-e);
+  const bf16_t* wp = (const bf16_t*)w.data_ptr();
+  const bf16_t* bp = has_bias ? (const bf16_t*)b->data_ptr() : nullptr;
+  if (has_bias)
+    hipLaunchKernelGGL((expand1d_bf16_e4m3_kernel<true>), dim3(grid),
+                       dim3(256), 0, stream, x.data_ptr<float>(), wp, bp,
+                       (bf16_t*)out.data_ptr(),
+                       mask_out.data_ptr<unsigned char>(),
+                       out8.data_ptr<unsigned char>(), n, (int)(H / 8),
+                       inv_scale);
+  else
+    hipLaunchKernelGGL((expand1d_bf16_e4m3_kernel<false>), dim3(grid),
+                       dim3(256), 0, stream, x.data_ptr<float>(), wp, bp,
+                       (bf16_t*)out.data_ptr(),
+                       mask_out.data_ptr<unsigned char>(),
+                       out8.data_ptr<unsigned char>(), n, (int)(H / 8),
+                       inv_scale);
+  return {out, mask_out, out8};
+}
+
 at::Tensor quantize_e4m3_hip(const at::Tensor& x, int64_t e) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous(), "quantize_e4m3: cuda contig");
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16 ||
@@ -688,11 +787,11 @@ at::Tensor gemm_mx8_nt_hip(const at::Tensor& a8, int64_t ea,
     if (mx_one_phase())                                                     \
       hipLaunchKernelGGL((gemm_mx8_nt_1p_kernel<EPI_, HB_, OF_>), grid,     \
                          dim3(MX_THREADS), 0, stream, ap, bp, bias_p,       \
-                         nullptr, C.data_ptr(), M, N, K, sa, sb);           \
+                         nullptr, nullptr, C.data_ptr(), M, N, K, sa, sb);  \
     else                                                                    \
       hipLaunchKernelGGL((gemm_mx8_nt_kernel<EPI_, HB_, OF_>), grid,        \
                          dim3(MX_THREADS), 0, stream, ap, bp, bias_p,       \
-                         nullptr, C.data_ptr(), M, N, K, sa, sb,            \
+                         nullptr, nullptr, C.data_ptr(), M, N, K, sa, sb,   \
                          mx_supertile(), mx_xcd_aware());                   \
   } while (0)
   if (relu) {
@@ -740,13 +839,71 @@ at::Tensor gemm_mx8_relu_dot_hip(const at::Tensor& a8, int64_t ea,
                        grid, dim3(MX_THREADS), 0, stream,
                        a8.data_ptr<unsigned char>(),
                        b8.data_ptr<unsigned char>(), b2.data_ptr<float>(),
-                       w3.data_ptr<float>(), y.data_ptr(), M, N, K, sa, sb);
+                       w3.data_ptr<float>(), nullptr, y.data_ptr(), M, N, K,
+                       sa, sb);
   else
     hipLaunchKernelGGL((gemm_mx8_nt_kernel<MX_EPI_RELU_DOT, true, true>),
                        grid, dim3(MX_THREADS), 0, stream,
                        a8.data_ptr<unsigned char>(),
                        b8.data_ptr<unsigned char>(), b2.data_ptr<float>(),
-                       w3.data_ptr<float>(), y.data_ptr(), M, N, K, sa, sb,
-                       mx_supertile(), mx_xcd_aware());
+                       w3.data_ptr<float>(), nullptr, y.data_ptr(), M, N, K,
+                       sa, sb, mx_supertile(), mx_xcd_aware());
   return y;
+}
+
+// (h2, mask) = relu(a8.b8^T dequant + bias) as bf16 AND its 1-bit ReLU
+// mask (uint8 [M, N/8]) in one pass — the MLP fp8 TRAINING forward's h2
+// GEMM (the MX twin of linear_relu_mask_bf16).  h2 is bit-identical to
+// gemm_mx8_nt(..., relu=true, out_fp32=false).
+std::tuple<at::Tensor, at::Tensor> gemm_mx8_relu_mask_hip(
+    const at::Tensor& a8, int64_t ea, const at::Tensor& b8, int64_t eb,
+    const c10::optional<at::Tensor>& bias) {
+  TORCH_CHECK(a8.is_cuda() && b8.is_cuda(), "gemm_mx8_relu_mask: cuda tensors");
+  TORCH_CHECK(a8.scalar_type() == torch::kUInt8 &&
+                  b8.scalar_type() == torch::kUInt8,
+              "gemm_mx8_relu_mask: e4m3 byte tensors");
+  TORCH_CHECK(a8.dim() == 2 && b8.dim() == 2 && a8.size(1) == b8.size(1),
+              "gemm_mx8_relu_mask: [M,K]x[N,K]");
+  TORCH_CHECK(a8.is_contiguous() && b8.is_contiguous(), "contiguous");
+  long long M = a8.size(0), K = a8.size(1), N = b8.size(0);
+  TORCH_CHECK(M % MX_BM == 0 && N % MX_BN == 0 && K % MX_BK == 0,
+              "gemm_mx8_relu_mask requires M%256==0, N%256==0, K%128==0 "
+              "(got ", M, "x", N, "x", K, ")");
+  int sa = (int)(ea + 127), sb = (int)(eb + 127);
+  TORCH_CHECK(0 <= sa && sa <= 254 && 0 <= sb && sb <= 254,
+              "per-tensor exponent out of E8M0 range");
+  auto C = torch::empty({M, N}, a8.options().dtype(torch::kBFloat16));
+  auto mask = torch::empty({M, N / 8}, a8.options());
+  if (M == 0 || N == 0) return {C, mask};
+  const float* bias_p = nullptr;
+  bool has_bias = false;
+  if (bias.has_value() && bias->defined()) {
+    TORCH_CHECK(bias->is_cuda() && bias->scalar_type() == torch::kFloat &&
+                    bias->numel() == N && bias->is_contiguous(),
+                "bias: fp32 [N] cuda");
+    bias_p = bias->data_ptr<float>();
+    has_bias = true;
+  }
+  dim3 grid((unsigned)(N / MX_BN), (unsigned)(M / MX_BM));
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const unsigned char* ap = a8.data_ptr<unsigned char>();
+  const unsigned char* bp = b8.data_ptr<unsigned char>();
+  unsigned char* mp = mask.data_ptr<unsigned char>();
+#define LMXM(HB_)                                                           \
+  do {                                                                      \
+    if (mx_one_phase())                                                     \
+      hipLaunchKernelGGL(                                                   \
+          (gemm_mx8_nt_1p_kernel<MX_EPI_BIAS_RELU, HB_, false, true>),      \
+          grid, dim3(MX_THREADS), 0, stream, ap, bp, bias_p, nullptr, mp,   \
+          C.data_ptr(), M, N, K, sa, sb);                                   \
+    else                                                                    \
+      hipLaunchKernelGGL(                                                   \
+          (gemm_mx8_nt_kernel<MX_EPI_BIAS_RELU, HB_, false, true>), grid,   \
+          dim3(MX_THREADS), 0, stream, ap, bp, bias_p, nullptr, mp,         \
+          C.data_ptr(), M, N, K, sa, sb, mx_supertile(), mx_xcd_aware());   \
+  } while (0)
+  if (has_bias) LMXM(true);
+  else          LMXM(false);
+#undef LMXM
+  return {C, mask};
 }

@@ -124,6 +124,20 @@ def run_loop(
     return results
 
 
+def resolve_model(name: str) -> tuple[str, dict[str, str]]:
+    """Map a ``--model`` name to (model_type, env flags to set).
+
+    ``mlp-fp8`` is the MLP with the MX-fp8 scoring forward;
+    ``mlp-fp8-train`` additionally runs the training forward's h2 GEMM
+    in MX-fp8.  Every other name passes through unchanged."""
+    if name == "mlp-fp8":
+        return "mlp", {"BODYWORK_MLP_FP8": "1"}
+    if name == "mlp-fp8-train":
+        return "mlp", {"BODYWORK_MLP_FP8": "1",
+                       "BODYWORK_MLP_FP8_TRAIN": "1"}
+    return name, {}
+
+
 def main(argv=None) -> None:
     p = argparse.ArgumentParser(description=__doc__)
     p.add_argument("--store", default=None)
@@ -131,7 +145,9 @@ def main(argv=None) -> None:
     p.add_argument("--rows", type=int, default=24 * 60)
     p.add_argument("--model", default="linear",
                    help="linear | poly[<degree>] | mlp | mlp-fp8 "
-                        "(mlp with the MX-fp8 scoring forward)")
+                        "(mlp with the MX-fp8 scoring forward) | "
+                        "mlp-fp8-train (mlp-fp8 plus the MX-fp8 training "
+                        "forward)")
     p.add_argument("--device", default=None)
     p.add_argument("--start-date", default="2026-01-01")
     p.add_argument("--format", default="csv", choices=["csv", "npy"])
@@ -140,11 +156,12 @@ def main(argv=None) -> None:
                    choices=["always", "drift"])
     p.add_argument("--drift-threshold", type=float, default=1.5)
     args = p.parse_args(argv)
-    if args.model == "mlp-fp8":  # env flag so the deployed scorer opts in
+    # env flags so the models built inside the cycle opt in
+    args.model, env = resolve_model(args.model)
+    if env:
         import os
 
-        os.environ["BODYWORK_MLP_FP8"] = "1"
-        args.model = "mlp"
+        os.environ.update(env)
     results = run_loop(
         open_store(args.store), days=args.days, n_rows=args.rows,
         model_type=args.model, device=args.device,

@@ -138,16 +138,53 @@ def bench() -> None:
               f"GB/s read)")
 
 
+def bench_train_forward(m: int, n: int, k: int) -> None:
+    """The fp8 TRAINING forward's h2 GEMM (bf16 out + 1-bit relu mask)
+    against the bf16 kernel it replaces, same shape, plus the layer-1
+    expand each path needs (dual-emit vs bf16+mask only)."""
+    g = torch.Generator(device="cuda").manual_seed(3)
+    a = torch.randn(m, k, generator=g, device="cuda").relu_()
+    b = torch.randn(n, k, generator=g, device="cuda") * (2.0 / k) ** 0.5
+    bias = torch.randn(n, generator=g, device="cuda") * 0.1
+    a8, ea = _quant(a)
+    b8, eb = _quant(b)
+    abf, bbf, bias_bf = a.bfloat16(), b.bfloat16(), bias.bfloat16()
+    fl = 2.0 * m * n * k
+    t8 = _time_gemm(lambda: ops.gemm_mx8_relu_mask(a8, ea, b8, eb, bias))
+    tb = _time_gemm(lambda: ops.linear_relu_mask_bf16(abf, bbf, bias_bf))
+    print(f"train-forward {m}x{n}x{k}: gemm_mx8_relu_mask "
+          f"{t8 * 1e3:.3f} ms ({fl / t8 / 1e12:.0f} TF) | "
+          f"linear_relu_mask_bf16 {tb * 1e3:.3f} ms "
+          f"({fl / tb / 1e12:.0f} TF) | ratio {tb / t8:.2f}x")
+    x = torch.randn(m, generator=g, device="cuda")
+    w1 = torch.randn(k, generator=g, device="cuda").bfloat16()
+    b1 = torch.randn(k, generator=g, device="cuda").bfloat16()
+    e1 = ops.e4m3_exponent(8.0)
+    td = _time_gemm(lambda: ops.expand1d_bf16_e4m3(x, w1, b1, e1))
+    te = _time_gemm(lambda: ops.expand1d_bf16(x, w1, b1, relu=True,
+                                              emit_mask=True))
+    print(f"layer-1 expand {m}x{k}: dual-emit {td * 1e3:.3f} ms | "
+          f"bf16+mask {te * 1e3:.3f} ms | extra {(td - te) * 1e3:.3f} ms | "
+          f"net forward saving {(tb - t8 - (td - te)) * 1e3:.3f} ms")
+
+
 def main() -> None:
     p = argparse.ArgumentParser()
     p.add_argument("--check", action="store_true")
     p.add_argument("--bench", action="store_true")
+    p.add_argument("--bench-train", action="store_true",
+                   help="time gemm_mx8_relu_mask against "
+                        "linear_relu_mask_bf16 at --shape")
+    p.add_argument("--shape", default="65536x4096x4096",
+                   help="MxNxK for --bench-train")
     args = p.parse_args()
     rc = 0
-    if args.check or not args.bench:
+    if args.check or not (args.bench or args.bench_train):
         rc = check()
     if args.bench:
         bench()
+    if args.bench_train:
+        bench_train_forward(*(int(v) for v in args.shape.split("x")))
     raise SystemExit(rc)
 
 
