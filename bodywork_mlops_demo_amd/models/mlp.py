@@ -16,7 +16,14 @@ hand-written bf16 MFMA kernels (fp32 accumulate), optimizer state fp32.
 In DP training gradients are bucket-all-reduced over RCCL.
 Opt-in (``fp8_training=True`` / ``BODYWORK_MLP_FP8_TRAIN=1``): the
 training forward's h2 GEMM runs on MX-fp8 (e4m3) operands with
-per-fit static exponents; the backward is unchanged.
+per-fit static exponents.  On top of that (``fp8_backward=True`` /
+``BODYWORK_MLP_FP8_BWD=1``) the two backward H x H GEMMs run on the same
+2x-rate scaled MFMA: the gradient ``dz2`` is quantised to e5m2 with a
+per-step exponent computed on the device (so the captured step graph
+stays valid), dgrad multiplies it with an e4m3 shadow of ``W2`` and
+applies the 1-bit ReLU mask in the epilogue, wgrad multiplies the
+byte-transposed e4m3 ``h1`` of the forward with the byte-transposed
+``dz2``.  Everything else in the backward stays bf16/fp32.
 
 Artefact: a *real sklearn ``MLPRegressor``* with ``coefs_``/``intercepts_``
 injected, so ``joblib.load`` + ``predict`` work with stock sklearn
@@ -51,7 +58,8 @@ class GPUMLPRegressor:
 
     def __init__(self, hidden: int = 4096, device="cpu", seed: int = 7,
                  fp8_scoring: bool | None = None,
-                 fp8_training: bool | None = None):
+                 fp8_training: bool | None = None,
+                 fp8_backward: bool | None = None):
         self.hidden = hidden
         self.device = canonical_device(device)
         # opt-in MX-fp8 scoring forward (2x-rate K=128 scaled MFMA for the
@@ -66,15 +74,31 @@ class GPUMLPRegressor:
         self._e_w2: int | None = None
         self._e_h1: int | None = None
         # opt-in MX-fp8 TRAINING forward: the h2 = relu(h1 @ W2 + b2) GEMM
-        # runs on e4m3 operands (the two backward GEMMs stay bf16 and the
-        # gradients pass straight through the quantisation).  Its shadow
-        # and exponents are separate from the scoring ones above.
-        if fp8_training is None:
-            import os as _os
+        # runs on e4m3 operands (with this flag alone the two backward
+        # GEMMs stay bf16 and the gradients pass straight through the
+        # quantisation).  Its shadow and exponents are separate from the
+        # scoring ones above.
+        # opt-in MX-fp8 BACKWARD GEMMs (e5m2 gradients) on top of it.  They
+        # consume the forward's e4m3 h1, so the flag implies the fp8
+        # forward; an explicit argument beats an environment flag.
+        import os as _os
 
-            fp8_training = _os.environ.get("BODYWORK_MLP_FP8_TRAIN",
+        bwd_explicit = fp8_backward is not None
+        if fp8_backward is None:
+            fp8_backward = _os.environ.get("BODYWORK_MLP_FP8_BWD",
                                            "0") == "1"
+        if fp8_backward and fp8_training is False:
+            if bwd_explicit:
+                raise ValueError(
+                    "fp8_backward=True needs the fp8 training forward "
+                    "(its e4m3 h1 is the wgrad operand); fp8_training="
+                    "False contradicts it")
+            fp8_backward = False  # an explicit argument beats the env flag
+        if fp8_training is None:
+            fp8_training = fp8_backward or _os.environ.get(
+                "BODYWORK_MLP_FP8_TRAIN", "0") == "1"
         self.fp8_training = fp8_training
+        self.fp8_backward = fp8_backward
         self._init_fp8_train_state()
         g = torch.Generator(device="cpu").manual_seed(seed)
         h = hidden
@@ -95,6 +119,7 @@ class GPUMLPRegressor:
             setattr(self, name, getattr(self, name).to(d))
         self._w2_q8 = None  # fp8 shadow re-created lazily on new device
         self._w2_q8_tr = None
+        self._w2t_q8_tr = None
         self._refresh_bf16()
 
     def _refresh_bf16(self):
@@ -156,6 +181,14 @@ class GPUMLPRegressor:
     # -- MX-fp8 training shadow ------------------------------------------
     def _init_fp8_train_state(self) -> None:
         self._w2_q8_tr: torch.Tensor | None = None
+        # second shadow for the fp8 dgrad: W2wt_bf ([in,out]) in e4m3 with
+        # the SAME static exponent
+        self._w2t_q8_tr: torch.Tensor | None = None
+        # e4m3 h1 of the latest fp8 training forward (the wgrad operand);
+        # _forward keeps its 6-tuple, so it travels here
+        self._h1q_tr: torch.Tensor | None = None
+        # which backward GEMMs the fp8 backward covers (A/B switch)
+        self._fp8_bwd_parts: frozenset[str] = frozenset(("dgrad", "wgrad"))
         self._e_w2_tr: int | None = None
         self._e_h1_tr: int | None = None
         self._xn_max_tr: float = self.XN_BOUND
@@ -191,6 +224,8 @@ class GPUMLPRegressor:
             self._w2_q8_tr = ops.quantize_e4m3(self.W2w_bf, self._e_w2_tr)
         else:
             self._refresh_fp8_train()
+        if self.fp8_backward and self._w2t_q8_tr is None:
+            self._w2t_q8_tr = ops.quantize_e4m3(self.W2wt_bf, self._e_w2_tr)
 
     def _refresh_fp8_train(self) -> None:
         """Requantise the training W2 shadow IN PLACE from ``W2w_bf``
@@ -199,6 +234,9 @@ class GPUMLPRegressor:
         if self._w2_q8_tr is None:
             return
         self._w2_q8_tr.copy_(ops.quantize_e4m3(self.W2w_bf, self._e_w2_tr))
+        if self._w2t_q8_tr is not None:
+            self._w2t_q8_tr.copy_(ops.quantize_e4m3(self.W2wt_bf,
+                                                    self._e_w2_tr))
 
     def _fp8_train_saturated(self) -> list[str]:
         """Names of the tensors whose current range exceeds what the
@@ -222,6 +260,17 @@ class GPUMLPRegressor:
         return (self.device.type != "cuda"
                 or (m % 256 == 0 and self.hidden % 256 == 0))
 
+    def _use_fp8_bwd(self, m: int) -> bool:
+        """MX-fp8 backward GEMMs: opt-in, gated like the fp8 forward they
+        depend on (GPU: batch and hidden tile multiples; CPU: the oracles
+        serve any shape whose hidden is a multiple of 16 — transpose_u8's
+        granularity, the batch being the other side).  Otherwise the bf16
+        backward runs."""
+        if not (self.fp8_backward and self._use_fp8_train(m)):
+            return False
+        return (self.device.type == "cuda"
+                or (m % 16 == 0 and self.hidden % 16 == 0))
+
     def parameters(self) -> list[torch.Tensor]:
         return [self.w1, self.b1, self.W2, self.b2, self.w3, self.b3]
 
@@ -239,6 +288,7 @@ class GPUMLPRegressor:
                 self._prepare_fp8_training()
             h1, m1, h1q = ops.expand1d_bf16_e4m3(xn, self.w1_bf, self.b1_bf,
                                                  self._e_h1_tr)
+            self._h1q_tr = h1q if self.fp8_backward else None
             h2, m2 = ops.gemm_mx8_relu_mask(h1q, self._e_h1_tr,
                                             self._w2_q8_tr, self._e_w2_tr,
                                             self.b2)
@@ -447,9 +497,14 @@ class GPUMLPRegressor:
         # a change in the flag or either exponent needs a new graph
         fp8_key = ((True, self._e_w2_tr, self._e_h1_tr)
                    if self.fp8_training else (False, None, None))
+        # the fp8 backward changes the captured kernels (its gradient
+        # exponent is a device tensor, so it needs no key of its own)
+        bwd_key = (bool(self.fp8_backward),
+                   tuple(sorted(self._fp8_bwd_parts)))
         if (st is None or st["cap"] < n or st["bs"] != bs or st["lr"] != lr
                 or st.get("world", 1) != world
-                or st.get("fp8_key") != fp8_key):
+                or st.get("fp8_key") != fp8_key
+                or st.get("bwd_key") != bwd_key):
             cap = max(n, int(st["cap"]) if st else 0)
             st = {
                 "cap": cap, "bs": bs, "lr": lr,
@@ -459,6 +514,7 @@ class GPUMLPRegressor:
                 "ctr": torch.zeros(1, dtype=torch.int64, device=self.device),
                 "bc": torch.ones(2, device=self.device),
                 "graph": None, "world": world, "fp8_key": fp8_key,
+                "bwd_key": bwd_key,
             }
             self._train_static = st
         st["X"][:n].copy_(X)
@@ -531,11 +587,30 @@ class GPUMLPRegressor:
         dw3 = ops.coldot_bf16(h2, dy)                           # (H,)
         db3 = dy.sum().reshape(1)
         # dh2 = outer(dy, w3) * relu'(h2): fused expand with 1-bit mask
-        dz2 = ops.expand1d_bf16(dy, self.w3_bf, None, relu=False, mask=m2)
+        fp8_bwd = self._use_fp8_bwd(nb)
+        if fp8_bwd:
+            # per-step gradient scale ON THE DEVICE (graph-safe):
+            # |dz2| <= max|dy| * max|w3|, so nothing saturates
+            e_g = ops.amax_exponent_e5m2(dy, self.w3_bf)
+            dz2, dz2q = ops.expand1d_bf16_e5m2(dy, self.w3_bf, m2, e_g)
+        else:
+            dz2 = ops.expand1d_bf16(dy, self.w3_bf, None, relu=False,
+                                    mask=m2)
         # layer 2: h2 = relu(h1 @ W2 + b2), W2 [in,out]
-        dW2 = ops.gemm_tn_bf16(h1, dz2, out_fp32=True)          # (in,out)
+        if fp8_bwd and "wgrad" in self._fp8_bwd_parts:
+            # both operands K-contiguous over the batch: byte transposes
+            dW2 = ops.gemm_mx8_nt_fmt(
+                ops.transpose_u8(self._h1q_tr), self._e_h1_tr,
+                ops.transpose_u8(dz2q), e_g, "e4m3", "e5m2", out_fp32=True)
+        else:
+            dW2 = ops.gemm_tn_bf16(h1, dz2, out_fp32=True)      # (in,out)
         db2 = ops.colsum_bf16(dz2)
-        dz1 = ops.linear_bf16(dz2, self.W2wt_bf, mask=m1)       # dz2 @ W2^T
+        if fp8_bwd and "dgrad" in self._fp8_bwd_parts:
+            dz1 = ops.gemm_mx8_nt_fmt(dz2q, e_g, self._w2t_q8_tr,
+                                      self._e_w2_tr, "e5m2", "e4m3",
+                                      mask=m1)                  # dz2 @ W2^T
+        else:
+            dz1 = ops.linear_bf16(dz2, self.W2wt_bf, mask=m1)   # dz2 @ W2^T
         # layer 1: h1 = relu(xn w1 + b1)
         dw1, db1 = ops.coldot_bf16(dz1, xn, also_colsum=True)
         return [dw1, db1, dW2, db2, dw3, db3]
@@ -609,8 +684,10 @@ class GPUMLPRegressor:
         self._w2_q8 = None
         self._e_w2 = None
         self._e_h1 = None
-        self.fp8_training = _os.environ.get("BODYWORK_MLP_FP8_TRAIN",
+        self.fp8_backward = _os.environ.get("BODYWORK_MLP_FP8_BWD",
                                             "0") == "1"
+        self.fp8_training = self.fp8_backward or _os.environ.get(
+            "BODYWORK_MLP_FP8_TRAIN", "0") == "1"
         self._init_fp8_train_state()
         self._to_device()
         return self

@@ -535,6 +535,125 @@ def expand1d_bf16_e4m3(
     return h, mask, expand1d_e4m3(x, w, b, e)
 
 
+# --------------------------------------------------------------------------
+# MX-fp8 training backward: e5m2 gradients, device exponents, mask-mul
+# --------------------------------------------------------------------------
+
+_MX_FMT = {"e4m3": 0, "e5m2": 1}
+
+
+def e5m2_exponent(amax: float) -> int:
+    """Per-tensor shared exponent for e5m2: smallest e with amax/2^e <=
+    57344 (no saturation), clamped to [-127, 127]; 0 for a zero or
+    non-finite amax.  Exact at the boundary (float field arithmetic)."""
+    return reference.e5m2_exponent(amax)
+
+
+def _split_exp(e, device: torch.device) -> tuple[int, torch.Tensor | None]:
+    """An exponent argument (Python int | int32[1] tensor) as the op's
+    (host int, optional device tensor) pair."""
+    if torch.is_tensor(e):
+        if e.dtype != torch.int32 or e.numel() != 1:
+            raise TypeError("a tensor exponent must be int32 with 1 element")
+        return 0, e.reshape(1).to(device)
+    return int(e), None
+
+
+def amax_exponent_e5m2(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """int32[1] e5m2 exponent of the bound ``max|x| * max|w|`` (fp32) on
+    every element of ``outer(x, w)`` — the per-step gradient scale of the
+    fp8 backward, computed ON THE DEVICE (one launch, no atomics, bitwise
+    deterministic, capturable) so a captured step never syncs.  Same rule
+    as :func:`e5m2_exponent`.  ``x`` fp32 [n], ``w`` bf16 [H]."""
+    if x.device.type == "cuda":
+        core = _core(x.device)
+        return core.amax_exponent_e5m2(x.contiguous().float(),
+                                       w.contiguous())
+    return reference.amax_exponent_e5m2_cpu(x, w)
+
+
+def quantize_e5m2(x: torch.Tensor, e) -> torch.Tensor:
+    """x -> OCP e5m2 byte codes with value = 2^e * stored (RNE, saturating
+    at +-57344 by an explicit clamp).  ``e`` is a Python int or an
+    int32[1] device tensor (read in-kernel).  CPU oracle: nearest value
+    on the finite grid, ties to the even code."""
+    if x.device.type == "cuda":
+        core = _core(x.device)
+        eh, ed = _split_exp(e, x.device)
+        return core.quantize_e5m2(x.contiguous(), eh, ed)
+    return reference.quantize_e5m2_cpu(x, e)
+
+
+def expand1d_bf16_e5m2(
+    x: torch.Tensor,
+    w: torch.Tensor,
+    mask: torch.Tensor,
+    e_dev: torch.Tensor,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """dz = outer(x, w) * bit(mask) emitted in ONE pass as (bf16 [n,H],
+    e5m2 bytes [n,H] with value = 2^e * stored) — the fp8 backward's
+    ``dz2``.  The bf16 output is bit-identical to
+    ``expand1d_bf16(x, w, None, relu=False, mask=mask)``; the bytes
+    quantise that bf16-rounded value; ``e_dev`` (int32[1]) is read
+    in-kernel.  CPU oracle: composition of those two ops."""
+    if x.device.type == "cuda":
+        core = _core(x.device)
+        return core.expand1d_bf16_e5m2(
+            x.contiguous().float(), w.contiguous(), mask.contiguous(),
+            _split_exp(e_dev, x.device)[1])
+    out = reference.expand1d_cpu(x, w, None, False, mask)
+    return out, reference.quantize_e5m2_cpu(out.float(), e_dev)
+
+
+def transpose_u8(src: torch.Tensor) -> torch.Tensor:
+    """[C,R] uint8 = [R,C] uint8 transposed (LDS-tiled, 16-B global I/O)
+    — makes the fp8 wgrad operands K-contiguous over the batch.  R and C
+    must be multiples of 16."""
+    if src.dim() != 2 or src.shape[0] % 16 or src.shape[1] % 16:
+        raise RuntimeError(
+            "transpose_u8 requires a 2-d tensor with rows%16==0 and "
+            f"cols%16==0 (got {tuple(src.shape)})")
+    if src.device.type == "cuda":
+        core = _core(src.device)
+        return core.transpose_u8(src.contiguous())
+    return src.t().contiguous()
+
+
+def gemm_mx8_nt_fmt(
+    a8: torch.Tensor,
+    ea,
+    b8: torch.Tensor,
+    eb,
+    a_fmt: str = "e4m3",
+    b_fmt: str = "e4m3",
+    mask: torch.Tensor | None = None,
+    out_fp32: bool = False,
+) -> torch.Tensor:
+    """C[M,N] = 2^(ea+eb) * (a8[M,K] . b8[N,K]^T) [* bit(mask)] with each
+    operand e4m3 or e5m2 — :func:`gemm_mx8_nt` generalised for the
+    training backward.
+
+    ``ea`` / ``eb`` are each a Python int or an int32[1] device tensor;
+    a tensor is read by the kernel at run time (clamped to the E8M0
+    range there), so a captured graph follows a per-step gradient scale.
+    ``mask`` is the 1-bit ReLU mask (uint8 [M, N/8]) of the dgrad
+    epilogue.  With the defaults the result is bit-identical to
+    ``gemm_mx8_nt``.  Requires M%256==0, N%256==0, K%128==0 on GPU.
+    CPU oracle: decode + fp32 matmul + mask."""
+    if a_fmt not in _MX_FMT or b_fmt not in _MX_FMT:
+        raise ValueError(f"fp8 format must be one of {sorted(_MX_FMT)}")
+    if a8.device.type == "cuda":
+        core = _core(a8.device)
+        eah, ead = _split_exp(ea, a8.device)
+        ebh, ebd = _split_exp(eb, a8.device)
+        return core.gemm_mx8_nt_fmt(
+            a8.contiguous(), eah, ead, b8.contiguous(), ebh, ebd,
+            _MX_FMT[a_fmt], _MX_FMT[b_fmt],
+            mask.contiguous() if mask is not None else None, out_fp32)
+    return reference.gemm_mx8_nt_fmt_cpu(a8, ea, b8, eb, a_fmt, b_fmt, mask,
+                                         out_fp32)
+
+
 def linear_relu_dot_bf16(
     x: torch.Tensor,
     w: torch.Tensor,

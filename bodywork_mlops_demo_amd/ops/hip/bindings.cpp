@@ -44,7 +44,7 @@ at::Tensor gemm_tn_bf16_hip(const at::Tensor& a, const at::Tensor& b,
 at::Tensor gemm8_relu_dot_bf16_hip(const at::Tensor& x, const at::Tensor& w,
                                    const at::Tensor& b2,
                                    const at::Tensor& w3);
-// gemm_mx8.hip — MX-fp8 (e4m3) K=128 scaled-MFMA path
+// gemm_mx8.hip — MX-fp8 (e4m3 / e5m2) K=128 scaled-MFMA path
 at::Tensor quantize_e4m3_hip(const at::Tensor& x, int64_t e);
 at::Tensor expand1d_e4m3_hip(const at::Tensor& x, const at::Tensor& w,
                              const c10::optional<at::Tensor>& b, int64_t e);
@@ -61,6 +61,20 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> expand1d_bf16_e4m3_hip(
 std::tuple<at::Tensor, at::Tensor> gemm_mx8_relu_mask_hip(
     const at::Tensor& a8, int64_t ea, const at::Tensor& b8, int64_t eb,
     const c10::optional<at::Tensor>& bias);
+at::Tensor amax_exponent_e5m2_hip(const at::Tensor& x, const at::Tensor& w);
+at::Tensor quantize_e5m2_hip(const at::Tensor& x, int64_t e,
+                             const c10::optional<at::Tensor>& e_dev);
+std::tuple<at::Tensor, at::Tensor> expand1d_bf16_e5m2_hip(
+    const at::Tensor& x, const at::Tensor& w, const at::Tensor& mask,
+    const at::Tensor& e_dev);
+at::Tensor transpose_u8_hip(const at::Tensor& src);
+at::Tensor gemm_mx8_nt_fmt_hip(const at::Tensor& a8, int64_t ea,
+                               const c10::optional<at::Tensor>& ea_dev,
+                               const at::Tensor& b8, int64_t eb,
+                               const c10::optional<at::Tensor>& eb_dev,
+                               int64_t a_fmt, int64_t b_fmt,
+                               const c10::optional<at::Tensor>& mask,
+                               bool out_fp32);
 // optim.hip
 void adam_step_hip(at::Tensor p, const at::Tensor& g, at::Tensor m,
                    at::Tensor v, const c10::optional<at::Tensor>& p_bf16,
@@ -102,6 +116,14 @@ TORCH_LIBRARY(bodywork_hip, m) {
         "(Tensor, Tensor, Tensor)");
   m.def("gemm_mx8_relu_mask(Tensor a8, int ea, Tensor b8, int eb, "
         "Tensor? bias) -> (Tensor, Tensor)");
+  m.def("amax_exponent_e5m2(Tensor x, Tensor w) -> Tensor");
+  m.def("quantize_e5m2(Tensor x, int e, Tensor? e_dev) -> Tensor");
+  m.def("expand1d_bf16_e5m2(Tensor x, Tensor w, Tensor mask, Tensor e_dev) "
+        "-> (Tensor, Tensor)");
+  m.def("transpose_u8(Tensor src) -> Tensor");
+  m.def("gemm_mx8_nt_fmt(Tensor a8, int ea, Tensor? ea_dev, Tensor b8, "
+        "int eb, Tensor? eb_dev, int a_fmt, int b_fmt, Tensor? mask, "
+        "bool out_fp32) -> Tensor");
   m.def("gemm8_relu_dot_bf16(Tensor x, Tensor w, Tensor b2, Tensor w3) "
         "-> Tensor");
   m.def("adam_step(Tensor(a!) p, Tensor g, Tensor(b!) m, Tensor(c!) v, "
@@ -135,6 +157,11 @@ TORCH_LIBRARY_IMPL(bodywork_hip, CUDA, m) {
   m.impl("gemm_mx8_relu_dot", gemm_mx8_relu_dot_hip);
   m.impl("expand1d_bf16_e4m3", expand1d_bf16_e4m3_hip);
   m.impl("gemm_mx8_relu_mask", gemm_mx8_relu_mask_hip);
+  m.impl("amax_exponent_e5m2", amax_exponent_e5m2_hip);
+  m.impl("quantize_e5m2", quantize_e5m2_hip);
+  m.impl("expand1d_bf16_e5m2", expand1d_bf16_e5m2_hip);
+  m.impl("transpose_u8", transpose_u8_hip);
+  m.impl("gemm_mx8_nt_fmt", gemm_mx8_nt_fmt_hip);
   m.impl("gemm8_relu_dot_bf16", gemm8_relu_dot_bf16_hip);
   m.impl("adam_step", adam_step_hip);
   m.impl("batch_indices", batch_indices_hip);

@@ -1,4 +1,4 @@
-// MX-FP8 (e4m3) 256x256-tile NT GEMM for gfx950 — the 2x-rate
+// MX-FP8 (e4m3 / e5m2) 256x256-tile NT GEMM for gfx950 — the 2x-rate
 // low-precision path.  TWO schedules live here:
 //   - gemm_mx8_nt_1p_kernel (DEFAULT): single-phase-per-tile, 1 barrier
 //     per K-tile, B triple-buffered into the full 160 KB LDS — PMC
@@ -34,6 +34,13 @@
 // (E8M0); C = 2^(ea+eb) * (Aq . Bq) accumulated in fp32 by the MFMA.
 // Power-of-two scaling keeps dequantisation exact.
 //
+// Training backward (gemm_mx8_nt_fmt): either operand may be e5m2 (the
+// gradient format — the MFMA's cbsz/blgp immediates select it, both
+// formats are one byte so the memory system is unchanged), either
+// exponent may carry a per-step part read from device memory before the
+// K-loop (so a captured step graph follows the gradient scale), and the
+// MX_EPI_MASK_MUL epilogue applies a 1-bit ReLU mask (dz1 = ... * m1).
+//
 // The reference computes its scoring forward in fp64 sklearn
 // (stage_2_serve_model.py:78); this kernel is the opt-in low-precision
 // serving/training path with MAPE parity gates in the tests.
@@ -56,6 +63,26 @@ typedef __attribute__((ext_vector_type(4))) float mx_f32x4;
 #define MX_EPI_NONE 0
 #define MX_EPI_BIAS_RELU 1
 #define MX_EPI_RELU_DOT 2  // y[row] += sum_col relu(acc+bias)*w3[col]
+#define MX_EPI_MASK_MUL 3  // C = acc * bit(mask_in[row, col]) (ReLU backward)
+
+// operand formats = the scaled MFMA's cbsz (A) / blgp (B) immediates
+#define MX_FMT_E4M3 0
+#define MX_FMT_E5M2 1
+
+// DEV_SCALE: sa/sb arrive as (host exponent + 127), NOT range-checked;
+// add the int32 unbiased exponent behind each non-null pointer and clamp
+// to the E8M0 range.  One uniform load per operand, before the K-loop.
+template <bool DEV_SCALE>
+__device__ __forceinline__ void mx_dev_scales(int& sa, int& sb,
+                                              const int* __restrict__ ea_dev,
+                                              const int* __restrict__ eb_dev) {
+  if (DEV_SCALE) {
+    if (ea_dev) sa += *ea_dev;
+    if (eb_dev) sb += *eb_dev;
+    sa = min(max(sa, 0), 254);
+    sb = min(max(sb, 0), 254);
+  }
+}
 
 __device__ __forceinline__ void mx_glds16(const void* gsrc, void* lds_dst) {
   __builtin_amdgcn_global_load_lds(
@@ -80,7 +107,8 @@ __device__ __forceinline__ void mx_epilogue(
     mx_f32x4 (&acc)[4][4], const float* __restrict__ bias,
     const float* __restrict__ w3, unsigned char* __restrict__ mask_out,
     void* __restrict__ C, long long M, long long N, long long m0,
-    long long n0, int wm, int wn, int fl, int kg) {
+    long long n0, int wm, int wn, int fl, int kg,
+    const unsigned char* __restrict__ mask_in = nullptr) {
   if (EPI == MX_EPI_RELU_DOT) {
     // fused scoring head: y[row] += sum_col relu(acc + b2[col]) *
     // w3[col] — the h2 activation tensor is never materialised (saves
@@ -118,6 +146,20 @@ __device__ __forceinline__ void mx_epilogue(
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
+    // MASK_MUL: the wave's 64-column strip of a row is ONE 8-byte mask
+    // word (N % 256 == 0, so strips are whole and 8-byte aligned); read
+    // here, after the accumulators are final, as g8_epilogue does
+    unsigned long long mrow[4];
+    if (EPI == MX_EPI_MASK_MUL) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        long long row = m0 + wm * 64 + i * 16 + kg * 4 + r;
+        mrow[r] = row < M ? *(const unsigned long long*)(mask_in +
+                                                         row * (N >> 3) +
+                                                         ((n0 + wn * 64) >> 3))
+                          : 0ull;
+      }
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       long long col = n0 + wn * 64 + j * 16 + fl;
@@ -131,6 +173,8 @@ __device__ __forceinline__ void mx_epilogue(
         if (EPI == MX_EPI_BIAS_RELU) {
           v += bval;
           v = fmaxf(v, 0.0f);
+        } else if (EPI == MX_EPI_MASK_MUL) {
+          v = (mrow[r] >> (j * 16 + fl)) & 1 ? v : 0.0f;
         }
         if (EMIT_MASK) {
           // wave-wide ballot OUTSIDE the row/col conditional; lane
@@ -154,17 +198,23 @@ __device__ __forceinline__ void mx_epilogue(
   }
 }
 
-template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false>
+template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false,
+          int AFMT = MX_FMT_E4M3, int BFMT = MX_FMT_E4M3,
+          bool DEV_SCALE = false>
 __launch_bounds__(MX_THREADS)
 __global__ void gemm_mx8_nt_kernel(
-    const unsigned char* __restrict__ A,  // [M,K] e4m3, row-major
-    const unsigned char* __restrict__ B,  // [N,K] e4m3, row-major
+    const unsigned char* __restrict__ A,  // [M,K] fp8 (AFMT), row-major
+    const unsigned char* __restrict__ B,  // [N,K] fp8 (BFMT), row-major
     const float* __restrict__ bias, const float* __restrict__ w3,
     unsigned char* __restrict__ mask_out, void* __restrict__ C, long long M,
     long long N, long long K, int sa, int sb,
     int super,      // supertile height in y-blocks (sa/sb: E8M0 bytes)
-    int xcd_aware) {
+    int xcd_aware,
+    const int* __restrict__ ea_dev = nullptr,  // DEV_SCALE only
+    const int* __restrict__ eb_dev = nullptr,
+    const unsigned char* __restrict__ mask_in = nullptr) {  // MASK_MUL only
   __shared__ char lds[8 * MX_HTB];  // ONE __shared__ object (guide trap (a))
+  mx_dev_scales<DEV_SCALE>(sa, sb, ea_dev, eb_dev);
   // Supertile blockIdx remap (super > 1): consecutive dispatch ids walk
   // an (x-cols x super-rows) PATCH instead of a full grid-x row, so the
   // ~256 concurrently-resident workgroups (1 block/CU) touch
@@ -281,7 +331,7 @@ __global__ void gemm_mx8_nt_kernel(
 #define MX_MFMA(acc_i, afrag)                                               \
   _Pragma("unroll") for (int nf = 0; nf < 4; ++nf)                          \
       acc[acc_i][nf] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(    \
-          afrag, b_t[nf], acc[acc_i][nf], 0, 0, 0, sa, 0, sb)
+          afrag, b_t[nf], acc[acc_i][nf], AFMT, BFMT, 0, sa, 0, sb)
 
 #define MX_PHASE_A(T, TPAR)                                                 \
   do {                                                                      \
@@ -340,7 +390,7 @@ __global__ void gemm_mx8_nt_kernel(
 #undef MX_BSLOT
 
   mx_epilogue<EPI, HAS_BIAS, OUT_FP32, EMIT_MASK>(
-      acc, bias, w3, mask_out, C, M, N, m0, n0, wm, wn, fl, kg);
+      acc, bias, w3, mask_out, C, M, N, m0, n0, wm, wn, fl, kg, mask_in);
 }
 
 // ---- per-tensor e4m3 quantisation ----------------------------------------
@@ -402,14 +452,20 @@ __global__ void quantize_e4m3_kernel(const T* __restrict__ x,
 #define P1_ASLOT(buf, half) (lds + ((buf) * 2 + (half)) * MX_HTB)
 #define P1_BSLOT(buf, half) (lds + (4 + (buf) * 2 + (half)) * MX_HTB)
 
-template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false>
+template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false,
+          int AFMT = MX_FMT_E4M3, int BFMT = MX_FMT_E4M3,
+          bool DEV_SCALE = false>
 __launch_bounds__(MX_THREADS)
 __global__ void gemm_mx8_nt_1p_kernel(
     const unsigned char* __restrict__ A, const unsigned char* __restrict__ B,
     const float* __restrict__ bias, const float* __restrict__ w3,
     unsigned char* __restrict__ mask_out, void* __restrict__ C, long long M,
-    long long N, long long K, int sa, int sb) {
+    long long N, long long K, int sa, int sb,
+    const int* __restrict__ ea_dev = nullptr,  // DEV_SCALE only
+    const int* __restrict__ eb_dev = nullptr,
+    const unsigned char* __restrict__ mask_in = nullptr) {  // MASK_MUL only
   __shared__ char lds[10 * MX_HTB];  // A 2 slots + B 3 slots, 160 KB
+  mx_dev_scales<DEV_SCALE>(sa, sb, ea_dev, eb_dev);
   const long long m0 = (long long)blockIdx.y * MX_BM;
   const long long n0 = (long long)blockIdx.x * MX_BN;
   const int wave = threadIdx.x >> 6;
@@ -478,7 +534,7 @@ __global__ void gemm_mx8_nt_1p_kernel(
 #define P1_MFMA(acc_i, afrag)                                               \
   _Pragma("unroll") for (int nf = 0; nf < 4; ++nf)                          \
       acc[acc_i][nf] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(    \
-          afrag, b_t[nf], acc[acc_i][nf], 0, 0, 0, sa, 0, sb)
+          afrag, b_t[nf], acc[acc_i][nf], AFMT, BFMT, 0, sa, 0, sb)
 
   for (int t = 0; t < nt; ++t) {
     if (t + 1 < nt)
@@ -525,7 +581,7 @@ __global__ void gemm_mx8_nt_1p_kernel(
 #undef P1_BR_BASE
 
   mx_epilogue<EPI, HAS_BIAS, OUT_FP32, EMIT_MASK>(
-      acc, bias, w3, mask_out, C, M, N, m0, n0, wm, wn, fl, kg);
+      acc, bias, w3, mask_out, C, M, N, m0, n0, wm, wn, fl, kg, mask_in);
 }
 
 // ---- fused rank-1 expand -> e4m3 ------------------------------------------
@@ -610,6 +666,208 @@ __global__ void expand1d_bf16_e4m3_kernel(
     mask_out[row * h8 + c8] = mb;
     store_bf16x8(out + o, f32_to_bf16x8(acc));
     *(unsigned long long*)(out8 + o) = packed;
+  }
+}
+
+// ---- e5m2 (gradient format) support kernels -------------------------------
+//
+// OCP e5m2 (S.EEEEE.MM, bias 15, max finite 57344, inf at 0x7C).  The
+// scaled value is clamped to +-57344 in plain code BEFORE the packed
+// convert, so saturation is defined here and never by the instruction's
+// overflow mode; NaN passes through the comparisons unchanged.
+__device__ __forceinline__ float mx_e5m2_prescale(float v, int e) {
+  v = ldexpf(v, -e);  // exact power-of-two scaling for any e in [-127,127]
+  v = v > 57344.0f ? 57344.0f : v;
+  v = v < -57344.0f ? -57344.0f : v;
+  return v;
+}
+
+// two floats -> two e5m2 bytes (RNE) in the low 16 bits
+__device__ __forceinline__ unsigned int mx_cvt2_e5m2(float v0, float v1) {
+  return (unsigned int)__builtin_amdgcn_cvt_pk_bf8_f32(v0, v1, 0, false) &
+         0xFFFFu;
+}
+
+// Per-step gradient exponent, computed on the device so a captured step
+// never syncs: a = max|x| * max|w| (fp32) bounds every |x[i]*w[j]|
+// because fp32 multiplication is monotone; out[0] = smallest e with
+// a / 2^e <= 57344, clamped to [-127,127]; 0 when a is 0 or non-finite.
+// The maxima are taken over the |value| BIT PATTERNS (monotone as
+// unsigned ints, NaN/inf sort above every finite value), so a NaN input
+// reaches the final test instead of being dropped by fmaxf.  The
+// exponent comes from the float's fields (a = 1.f * 2^(E-127), and
+// 57344 = 1.75 * 2^15), so the boundary is exact.  ONE block, no
+// atomics, order-independent integer max -> bitwise deterministic.
+__launch_bounds__(1024)
+__global__ void amax_exponent_e5m2_kernel(const float* __restrict__ x,
+                                          long long n,
+                                          const bf16_t* __restrict__ w,
+                                          long long H,
+                                          int* __restrict__ out) {
+  __shared__ unsigned int red[2][16];
+  const int tid = (int)threadIdx.x;
+  unsigned int mx = 0u, mw = 0u;
+  for (long long i = tid; i < n; i += 1024)
+    mx = max(mx, __float_as_uint(x[i]) & 0x7FFFFFFFu);
+  for (long long i = tid; i < H; i += 1024)
+    mw = max(mw, __float_as_uint(bf16_to_f32(w[i])) & 0x7FFFFFFFu);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    mx = max(mx, (unsigned int)__shfl_xor((int)mx, off, 64));
+    mw = max(mw, (unsigned int)__shfl_xor((int)mw, off, 64));
+  }
+  if ((tid & 63) == 0) {
+    red[0][tid >> 6] = mx;
+    red[1][tid >> 6] = mw;
+  }
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int k = 1; k < 16; ++k) {
+      mx = max(mx, red[0][k]);
+      mw = max(mw, red[1][k]);
+    }
+    const float a = __uint_as_float(mx) * __uint_as_float(mw);
+    const unsigned int bits = __float_as_uint(a) & 0x7FFFFFFFu;
+    const int E = (int)(bits >> 23);
+    const unsigned int man = bits & 0x7FFFFFu;
+    int e;
+    if (bits == 0u || E == 255)
+      e = 0;  // zero, inf or nan
+    else if (E == 0)
+      e = -127;  // subnormal product: far below the clamp
+    else
+      e = E - 127 - (man <= 0x600000u ? 15 : 14);
+    out[0] = min(max(e, -127), 127);
+  }
+}
+
+// x (bf16 or fp32) -> e5m2 bytes, value = 2^e * stored; e = e_host +
+// (*e_dev if given).
+template <typename T>
+__global__ void quantize_e5m2_kernel(const T* __restrict__ x,
+                                     unsigned char* __restrict__ out,
+                                     long long n, int e_host,
+                                     const int* __restrict__ e_dev) {
+  const int e = e_host + (e_dev ? *e_dev : 0);
+  long long i = (long long)(blockIdx.x) * blockDim.x + threadIdx.x;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const long long pairs = (n + 1) / 2;
+  for (; i < pairs; i += stride) {
+    const bool has1 = i * 2 + 1 < n;
+    float v0, v1 = 0.0f;
+    if constexpr (sizeof(T) == 2) {
+      v0 = bf16_to_f32(((const bf16_t*)x)[i * 2]);
+      if (has1) v1 = bf16_to_f32(((const bf16_t*)x)[i * 2 + 1]);
+    } else {
+      v0 = ((const float*)x)[i * 2];
+      if (has1) v1 = ((const float*)x)[i * 2 + 1];
+    }
+    unsigned int pk =
+        mx_cvt2_e5m2(mx_e5m2_prescale(v0, e), mx_e5m2_prescale(v1, e));
+    if (has1)
+      *(unsigned short*)(out + i * 2) = (unsigned short)pk;
+    else
+      out[i * 2] = (unsigned char)(pk & 0xFFu);  // odd tail element
+  }
+}
+
+// Dual-emit masked rank-1 expand for the backward: dz2 = outer(x, w) *
+// bit(mask) as bf16 (bit-identical to expand1d_kernel<false, false, true,
+// false>; colsum for db2 reads it) AND as e5m2 bytes of the bf16-ROUNDED
+// value with the exponent read from e_dev (so it equals
+// quantize_e5m2(bf16 output, e_dev)).
+__global__ void expand1d_bf16_e5m2_kernel(
+    const float* __restrict__ x, const bf16_t* __restrict__ w,
+    const unsigned char* __restrict__ mask, const int* __restrict__ e_dev,
+    bf16_t* __restrict__ out, unsigned char* __restrict__ out8, long long n,
+    int h8 /* H/8 */) {
+  const int e = *e_dev;
+  const long long total = (long long)n * h8;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+       idx < total; idx += stride) {
+    const long long row = idx / h8;
+    const int c8 = (int)(idx % h8);
+    float xv = x[row];
+    float wv[8], acc[8], rb[8];
+    bf16x8_to_f32(load_bf16x8(w + c8 * 8), wv);
+    unsigned char mb = mask[row * h8 + c8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      acc[k] = xv * wv[k];
+      acc[k] = (mb >> k) & 1 ? acc[k] : 0.0f;
+    }
+    const bf16x8 ob = f32_to_bf16x8(acc);
+    bf16x8_to_f32(ob, rb);
+    unsigned long long packed = 0;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      unsigned int pk = mx_cvt2_e5m2(mx_e5m2_prescale(rb[2 * p], e),
+                                     mx_e5m2_prescale(rb[2 * p + 1], e));
+      packed |= (unsigned long long)pk << (16 * p);
+    }
+    const long long o = row * (long long)h8 * 8 + c8 * 8;
+    store_bf16x8(out + o, ob);
+    *(unsigned long long*)(out8 + o) = packed;
+  }
+}
+
+// Byte transpose dst[C,R] = src[R,C]^T for the wgrad operands (both must
+// be K-contiguous over the batch).  128(src rows) x 64(src cols) LDS
+// tile, 16-B global loads and stores; R % 16 == 0 and C % 16 == 0 (host
+// checked) make every 16-B chunk wholly inside or wholly outside, edge
+// tiles are guarded per chunk.  LDS rows are 17 dwords (68 B): the
+// column-gather of the write phase reads rows 16 apart, which the odd
+// dword stride spreads over distinct banks.
+#define TU8_TR 128
+#define TU8_TC 64
+__launch_bounds__(256)
+__global__ void transpose_u8_kernel(const unsigned char* __restrict__ src,
+                                    unsigned char* __restrict__ dst,
+                                    long long R, long long C) {
+  __shared__ unsigned int tile[TU8_TR][17];
+  const long long r0 = (long long)blockIdx.y * TU8_TR;
+  const long long c0 = (long long)blockIdx.x * TU8_TC;
+  const int tid = (int)threadIdx.x;
+  // load: 128 rows x 4 chunks = 512 chunks, 2 passes
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const int ch = tid & 3;
+    const int tr = (tid >> 2) + p * 64;
+    const long long r = r0 + tr;
+    const long long c = c0 + ch * 16;
+    if (r < R && c < C) {
+      const mx_i32x4 v = *(const mx_i32x4*)(src + r * C + c);
+      tile[tr][ch * 4 + 0] = (unsigned int)v[0];
+      tile[tr][ch * 4 + 1] = (unsigned int)v[1];
+      tile[tr][ch * 4 + 2] = (unsigned int)v[2];
+      tile[tr][ch * 4 + 3] = (unsigned int)v[3];
+    }
+  }
+  __syncthreads();
+  // store: out row = src col (64), out chunk = 16 src rows (8 chunks);
+  // pass p handles chunks 4p..4p+3 so a wave's four chunks sit 16 LDS
+  // rows apart (distinct banks) and 4 lanes fill 64 contiguous bytes
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const int tc = (tid & 3) + p * 4;
+    const int oc = tid >> 2;
+    const long long orow = c0 + oc;
+    const long long ocol = r0 + tc * 16;
+    if (orow < C && ocol < R) {
+      const unsigned char* tb = (const unsigned char*)&tile[0][0];
+      mx_i32x4 v;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        unsigned int wq = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          wq |= (unsigned int)tb[(tc * 16 + q * 4 + k) * 68 + oc] << (8 * k);
+        v[q] = (int)wq;
+      }
+      *(mx_i32x4*)(dst + orow * R + ocol) = v;
+    }
   }
 }
 
@@ -906,4 +1164,206 @@ std::tuple<at::Tensor, at::Tensor> gemm_mx8_relu_mask_hip(
   else          LMXM(false);
 #undef LMXM
   return {C, mask};
+}
+
+// ---- training-backward ops: e5m2 operands, device exponents, mask-mul -----
+
+// optional int32[1] device exponent -> pointer (nullptr when absent)
+static const int* mx_edev_ptr(const c10::optional<at::Tensor>& e,
+                              const at::Tensor& like, const char* what) {
+  if (!e.has_value() || !e->defined()) return nullptr;
+  TORCH_CHECK(e->is_cuda() && e->device() == like.device() &&
+                  e->scalar_type() == torch::kInt32 && e->numel() == 1,
+              what, ": device exponent must be an int32[1] tensor on the "
+              "operand's device");
+  return e->data_ptr<int>();
+}
+
+at::Tensor amax_exponent_e5m2_hip(const at::Tensor& x, const at::Tensor& w) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() &&
+                  x.scalar_type() == torch::kFloat,
+              "amax_exponent_e5m2: x must be contiguous fp32 cuda");
+  TORCH_CHECK(w.is_cuda() && w.is_contiguous() &&
+                  w.scalar_type() == torch::kBFloat16,
+              "amax_exponent_e5m2: w must be contiguous bf16 cuda");
+  auto out = torch::empty({1}, x.options().dtype(torch::kInt32));
+  auto stream = at::cuda::getCurrentCUDAStream();
+  hipLaunchKernelGGL(amax_exponent_e5m2_kernel, dim3(1), dim3(1024), 0,
+                     stream, x.data_ptr<float>(), (long long)x.numel(),
+                     (const bf16_t*)w.data_ptr(), (long long)w.numel(),
+                     out.data_ptr<int>());
+  return out;
+}
+
+at::Tensor quantize_e5m2_hip(const at::Tensor& x, int64_t e,
+                             const c10::optional<at::Tensor>& e_dev) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous(), "quantize_e5m2: cuda contig");
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 ||
+                  x.scalar_type() == torch::kFloat,
+              "quantize_e5m2: bf16 or fp32 input");
+  TORCH_CHECK(-127 <= e && e <= 127, "quantize_e5m2: exponent out of range");
+  const int* edp = mx_edev_ptr(e_dev, x, "quantize_e5m2");
+  auto out = torch::empty_like(x, x.options().dtype(torch::kUInt8));
+  long long n = x.numel();
+  if (n == 0) return out;
+  auto stream = at::cuda::getCurrentCUDAStream();
+  long long pairs = (n + 1) / 2;
+  int threads = 256;
+  int blocks = (int)std::min<long long>((pairs + threads - 1) / threads,
+                                        8192);
+  if (x.scalar_type() == torch::kBFloat16)
+    hipLaunchKernelGGL(quantize_e5m2_kernel<short>, dim3(blocks),
+                       dim3(threads), 0, stream, (const short*)x.data_ptr(),
+                       out.data_ptr<unsigned char>(), n, (int)e, edp);
+  else
+    hipLaunchKernelGGL(quantize_e5m2_kernel<float>, dim3(blocks),
+                       dim3(threads), 0, stream, x.data_ptr<float>(),
+                       out.data_ptr<unsigned char>(), n, (int)e, edp);
+  return out;
+}
+
+std::tuple<at::Tensor, at::Tensor> expand1d_bf16_e5m2_hip(
+    const at::Tensor& x, const at::Tensor& w, const at::Tensor& mask,
+    const at::Tensor& e_dev) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() &&
+                  x.scalar_type() == at::kFloat,
+              "expand1d_bf16_e5m2: x must be contiguous fp32 cuda");
+  TORCH_CHECK(w.is_cuda() && w.is_contiguous() &&
+                  w.scalar_type() == at::kBFloat16,
+              "expand1d_bf16_e5m2: w must be contiguous bf16 cuda");
+  const long long n = x.numel();
+  const long long H = w.numel();
+  TORCH_CHECK(H % 8 == 0, "expand1d_bf16_e5m2: H must be a multiple of 8");
+  TORCH_CHECK(mask.is_cuda() && mask.is_contiguous() &&
+                  mask.scalar_type() == at::kByte &&
+                  mask.numel() == n * (H / 8),
+              "expand1d_bf16_e5m2: mask must be uint8 [n, H/8] bitmask");
+  const int* edp =
+      mx_edev_ptr(c10::optional<at::Tensor>(e_dev), x, "expand1d_bf16_e5m2");
+  TORCH_CHECK(edp != nullptr, "expand1d_bf16_e5m2: e_dev required");
+  auto out = at::empty({n, H}, w.options());
+  auto out8 = at::empty({n, H}, w.options().dtype(at::kByte));
+  long long total = n * (H / 8);
+  if (total == 0) return {out, out8};
+  auto stream = at::cuda::getCurrentCUDAStream();
+  int grid = (int)std::min<long long>((total + 255) / 256, 2048);
+  hipLaunchKernelGGL(expand1d_bf16_e5m2_kernel, dim3(grid), dim3(256), 0,
+                     stream, x.data_ptr<float>(), (const bf16_t*)w.data_ptr(),
+                     mask.data_ptr<unsigned char>(), edp,
+                     (bf16_t*)out.data_ptr(), out8.data_ptr<unsigned char>(),
+                     n, (int)(H / 8));
+  return {out, out8};
+}
+
+at::Tensor transpose_u8_hip(const at::Tensor& src) {
+  TORCH_CHECK(src.is_cuda() && src.dim() == 2 && src.is_contiguous() &&
+                  src.scalar_type() == torch::kUInt8,
+              "transpose_u8: contiguous 2-d uint8 cuda tensor");
+  long long R = src.size(0), C = src.size(1);
+  TORCH_CHECK(R % 16 == 0 && C % 16 == 0,
+              "transpose_u8 requires rows%16==0 and cols%16==0 (got ", R, "x",
+              C, ")");
+  TORCH_CHECK((uintptr_t)src.data_ptr() % 16 == 0,
+              "transpose_u8: source must be 16-byte aligned");
+  auto dst = torch::empty({C, R}, src.options());
+  if (R == 0 || C == 0) return dst;
+  auto stream = at::cuda::getCurrentCUDAStream();
+  dim3 grid((unsigned)((C + TU8_TC - 1) / TU8_TC),
+            (unsigned)((R + TU8_TR - 1) / TU8_TR));
+  hipLaunchKernelGGL(transpose_u8_kernel, grid, dim3(256), 0, stream,
+                     src.data_ptr<unsigned char>(),
+                     dst.data_ptr<unsigned char>(), R, C);
+  return dst;
+}
+
+template <int EPI, bool OF, int AF, int BF>
+static void mx_launch_fmt(dim3 grid, hipStream_t stream,
+                          const unsigned char* ap, const unsigned char* bp,
+                          void* cp, long long M, long long N, long long K,
+                          int sa, int sb, const int* eap, const int* ebp,
+                          const unsigned char* mp) {
+  if (mx_one_phase())
+    hipLaunchKernelGGL(
+        (gemm_mx8_nt_1p_kernel<EPI, false, OF, false, AF, BF, true>), grid,
+        dim3(MX_THREADS), 0, stream, ap, bp, nullptr, nullptr, nullptr, cp, M,
+        N, K, sa, sb, eap, ebp, mp);
+  else
+    hipLaunchKernelGGL(
+        (gemm_mx8_nt_kernel<EPI, false, OF, false, AF, BF, true>), grid,
+        dim3(MX_THREADS), 0, stream, ap, bp, nullptr, nullptr, nullptr, cp, M,
+        N, K, sa, sb, mx_supertile(), mx_xcd_aware(), eap, ebp, mp);
+}
+
+// C[M,N] = 2^(ea+eb) * (A[M,K] . B[N,K]^T) [* bit(mask)], A and B each
+// e4m3 (fmt 0) or e5m2 (fmt 1); each exponent is ea (host int) plus the
+// int32[1] device tensor ea_dev when given (read in-kernel, clamped to
+// the E8M0 range there).  fp32 or bf16 output.
+at::Tensor gemm_mx8_nt_fmt_hip(const at::Tensor& a8, int64_t ea,
+                               const c10::optional<at::Tensor>& ea_dev,
+                               const at::Tensor& b8, int64_t eb,
+                               const c10::optional<at::Tensor>& eb_dev,
+                               int64_t a_fmt, int64_t b_fmt,
+                               const c10::optional<at::Tensor>& mask,
+                               bool out_fp32) {
+  TORCH_CHECK(a8.is_cuda() && b8.is_cuda(), "gemm_mx8_nt_fmt: cuda tensors");
+  TORCH_CHECK(a8.scalar_type() == torch::kUInt8 &&
+                  b8.scalar_type() == torch::kUInt8,
+              "gemm_mx8_nt_fmt: fp8 byte tensors");
+  TORCH_CHECK(a8.dim() == 2 && b8.dim() == 2 && a8.size(1) == b8.size(1),
+              "gemm_mx8_nt_fmt: [M,K]x[N,K]");
+  TORCH_CHECK(a8.is_contiguous() && b8.is_contiguous(), "contiguous");
+  TORCH_CHECK((a_fmt == MX_FMT_E4M3 || a_fmt == MX_FMT_E5M2) &&
+                  (b_fmt == MX_FMT_E4M3 || b_fmt == MX_FMT_E5M2),
+              "gemm_mx8_nt_fmt: format must be 0 (e4m3) or 1 (e5m2)");
+  long long M = a8.size(0), K = a8.size(1), N = b8.size(0);
+  TORCH_CHECK(M % MX_BM == 0 && N % MX_BN == 0 && K % MX_BK == 0,
+              "gemm_mx8_nt_fmt requires M%256==0, N%256==0, K%128==0 (got ",
+              M, "x", N, "x", K, ")");
+  TORCH_CHECK((uintptr_t)a8.data_ptr() % 16 == 0 &&
+                  (uintptr_t)b8.data_ptr() % 16 == 0,
+              "gemm_mx8_nt_fmt: operands must be 16-byte aligned");
+  const int* eap = mx_edev_ptr(ea_dev, a8, "gemm_mx8_nt_fmt");
+  const int* ebp = mx_edev_ptr(eb_dev, a8, "gemm_mx8_nt_fmt");
+  // host parts stay loud; the device parts are clamped in-kernel
+  TORCH_CHECK(-127 <= ea && ea <= 127 && -127 <= eb && eb <= 127,
+              "per-tensor exponent out of E8M0 range");
+  int sa = (int)ea + 127, sb = (int)eb + 127;
+  const unsigned char* mp = nullptr;
+  if (mask.has_value() && mask->defined()) {
+    TORCH_CHECK(mask->is_cuda() && mask->is_contiguous() &&
+                    mask->scalar_type() == torch::kUInt8 &&
+                    mask->numel() == M * (N / 8),
+                "gemm_mx8_nt_fmt: mask must be uint8 [M, N/8] bitmask");
+    TORCH_CHECK((uintptr_t)mask->data_ptr() % 8 == 0,
+                "gemm_mx8_nt_fmt: mask must be 8-byte aligned");
+    mp = mask->data_ptr<unsigned char>();
+  }
+  auto opts = a8.options().dtype(out_fp32 ? torch::kFloat : torch::kBFloat16);
+  auto C = torch::empty({M, N}, opts);
+  if (M == 0 || N == 0) return C;
+  dim3 grid((unsigned)(N / MX_BN), (unsigned)(M / MX_BM));
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+#define LFMT4(EPI_, OF_, AF_, BF_)                                          \
+  mx_launch_fmt<EPI_, OF_, AF_, BF_>(grid, stream,                          \
+                                     a8.data_ptr<unsigned char>(),          \
+                                     b8.data_ptr<unsigned char>(),          \
+                                     C.data_ptr(), M, N, K, sa, sb, eap,    \
+                                     ebp, mp)
+#define LFMT2(EPI_, OF_)                                                    \
+  do {                                                                      \
+    if (a_fmt == MX_FMT_E4M3) {                                             \
+      if (b_fmt == MX_FMT_E4M3) LFMT4(EPI_, OF_, MX_FMT_E4M3, MX_FMT_E4M3); \
+      else                      LFMT4(EPI_, OF_, MX_FMT_E4M3, MX_FMT_E5M2); \
+    } else {                                                                \
+      if (b_fmt == MX_FMT_E4M3) LFMT4(EPI_, OF_, MX_FMT_E5M2, MX_FMT_E4M3); \
+      else                      LFMT4(EPI_, OF_, MX_FMT_E5M2, MX_FMT_E5M2); \
+    }                                                                       \
+  } while (0)
+  if (mp) { if (out_fp32) LFMT2(MX_EPI_MASK_MUL, true);
+            else          LFMT2(MX_EPI_MASK_MUL, false); }
+  else    { if (out_fp32) LFMT2(MX_EPI_NONE, true);
+            else          LFMT2(MX_EPI_NONE, false); }
+#undef LFMT2
+#undef LFMT4
+  return C;
 }

@@ -354,3 +354,121 @@ def gemm_mx8_nt_cpu(a8: torch.Tensor, ea: int, b8: torch.Tensor, eb: int,
     if relu:
         c = torch.relu(c)
     return c if out_fp32 else c.to(torch.bfloat16)
+
+
+# --------------------------------------------------------------------------
+# OCP e5m2 oracle — the gradient format of the opt-in fp8 backward
+# --------------------------------------------------------------------------
+
+E5M2_MAX = 57344.0  # largest finite e5m2 value (0x7B)
+
+
+def _e5m2_table() -> np.ndarray:
+    """All 256 OCP e5m2 code values (S.EEEEE.MM, bias 15): +-inf at
+    0x7C/0xFC, NaN above them."""
+    codes = np.arange(256, dtype=np.uint8)
+    s = (codes >> 7) & 1
+    e = ((codes >> 2) & 0x1F).astype(np.int32)
+    m = codes & 3
+    v = np.where(e == 0, (m / 4.0) * 2.0 ** -14,
+                 (1.0 + m / 4.0) * (2.0 ** (e - 15)))
+    v = np.where((e == 31) & (m == 0), np.inf, v)
+    v = np.where((e == 31) & (m != 0), np.nan, v)
+    v = np.where(s == 1, -v, v)
+    return v.astype(np.float64)
+
+
+_E5M2 = _e5m2_table()
+# positive finite grid: codes 0x00..0x7B are monotone in value, so the
+# grid index IS the byte code
+_E5M2_POS = _E5M2[:0x7C].copy()
+
+
+def e5m2_exponent(amax: float) -> int:
+    """Per-tensor shared exponent for e5m2: smallest e with amax/2^e <=
+    57344, clamped to [-127, 127]; 0 for a zero or non-finite amax.
+
+    Field arithmetic, not log2, so the boundary is exact: with
+    amax = m * 2^x, m in [0.5, 1), and 57344 = 0.875 * 2^16, e = x - 16
+    if m <= 0.875 else x - 15."""
+    import math
+
+    amax = float(amax)
+    if not math.isfinite(amax) or amax <= 0.0:
+        return 0
+    m, x = math.frexp(amax)
+    e = x - 16 if m <= 0.875 else x - 15
+    return max(-127, min(127, e))
+
+
+def amax_exponent_e5m2_cpu(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """int32[1] exponent of the product bound max|x| * max|w| (fp32)."""
+    if x.numel() == 0 or w.numel() == 0:
+        a = 0.0
+    else:
+        xf = x.detach().float().abs()
+        wf = w.detach().float().abs()
+        # NaN-propagating maxima (torch.max propagates NaN), fp32 product
+        a = (xf.max() * wf.max()).item()
+    return torch.tensor([e5m2_exponent(a)], dtype=torch.int32)
+
+
+def _exp_int(e) -> int:
+    """A Python int or a 1-element (device) tensor exponent, as an int."""
+    return int(e.reshape(-1)[0]) if torch.is_tensor(e) else int(e)
+
+
+def quantize_e5m2_cpu(x: torch.Tensor, e) -> torch.Tensor:
+    """x / 2^e to the nearest value of the finite e5m2 grid, ties to the
+    even code, saturating at +-57344; returns byte codes.  The sign bit
+    is the input's (a negative value that rounds to zero gives 0x80)."""
+    e = _exp_int(e)
+    v = x.detach().to(torch.float64).cpu().numpy() / (2.0 ** e)
+    v = np.clip(v, -E5M2_MAX, E5M2_MAX)
+    mag = np.abs(v)
+    idx = np.searchsorted(_E5M2_POS, mag)
+    top = len(_E5M2_POS) - 1
+    lo_i = np.clip(idx - 1, 0, top)
+    hi_i = np.clip(idx, 0, top)
+    lo, hi = _E5M2_POS[lo_i], _E5M2_POS[hi_i]
+    d_lo, d_hi = mag - lo, hi - mag
+    code = np.where(d_hi < d_lo, hi_i, lo_i)
+    tie = d_hi == d_lo
+    code = np.where(tie, np.where(lo_i % 2 == 0, lo_i, hi_i), code)
+    code = np.where(mag == hi, hi_i, code)  # exact grid hits (incl. 0)
+    byte = code.astype(np.uint8)
+    # the sign bit follows the input's sign, zero included (0x80 is -0),
+    # as the hardware convert does
+    byte = np.where(np.signbit(v), byte | 0x80, byte)
+    return torch.from_numpy(byte.astype(np.uint8)).reshape(x.shape)
+
+
+def e5m2_decode_cpu(codes: torch.Tensor, e=0) -> torch.Tensor:
+    vals = _E5M2[codes.detach().cpu().numpy().astype(np.uint8)]
+    return torch.from_numpy(
+        (vals * (2.0 ** _exp_int(e))).astype(np.float32)).reshape(codes.shape)
+
+
+def fp8_decode_cpu(codes: torch.Tensor, e=0, fmt: str = "e4m3") -> torch.Tensor:
+    if fmt == "e4m3":
+        return e4m3_decode_cpu(codes, _exp_int(e))
+    if fmt == "e5m2":
+        return e5m2_decode_cpu(codes, e)
+    raise ValueError(f"unknown fp8 format {fmt!r} (e4m3 | e5m2)")
+
+
+def gemm_mx8_nt_fmt_cpu(a8: torch.Tensor, ea, b8: torch.Tensor, eb,
+                        a_fmt: str = "e4m3", b_fmt: str = "e4m3",
+                        mask: torch.Tensor | None = None,
+                        out_fp32: bool = False) -> torch.Tensor:
+    """Format-aware MX GEMM oracle: decode, fp32 matmul, optional 1-bit
+    mask.  Device-tensor exponents are simply read."""
+    a = fp8_decode_cpu(a8, ea, a_fmt)
+    b = fp8_decode_cpu(b8, eb, b_fmt)
+    c = a @ b.t()
+    if mask is not None:
+        # a select, as in the kernels: a masked-off element is 0 even
+        # where the accumulator is not finite
+        c = torch.where(unpack_relu_mask(mask.cpu(), c.shape[1]), c,
+                        torch.zeros_like(c))
+    return c if out_fp32 else c.to(torch.bfloat16)

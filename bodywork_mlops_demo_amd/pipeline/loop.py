@@ -129,12 +129,17 @@ def resolve_model(name: str) -> tuple[str, dict[str, str]]:
 
     ``mlp-fp8`` is the MLP with the MX-fp8 scoring forward;
     ``mlp-fp8-train`` additionally runs the training forward's h2 GEMM
-    in MX-fp8.  Every other name passes through unchanged."""
+    in MX-fp8, and ``mlp-fp8-train-bwd`` the two backward GEMMs as well
+    (e5m2 gradients).  Every other name passes through unchanged."""
     if name == "mlp-fp8":
         return "mlp", {"BODYWORK_MLP_FP8": "1"}
     if name == "mlp-fp8-train":
         return "mlp", {"BODYWORK_MLP_FP8": "1",
                        "BODYWORK_MLP_FP8_TRAIN": "1"}
+    if name == "mlp-fp8-train-bwd":
+        return "mlp", {"BODYWORK_MLP_FP8": "1",
+                       "BODYWORK_MLP_FP8_TRAIN": "1",
+                       "BODYWORK_MLP_FP8_BWD": "1"}
     return name, {}
 
 
@@ -147,7 +152,8 @@ def main(argv=None) -> None:
                    help="linear | poly[<degree>] | mlp | mlp-fp8 "
                         "(mlp with the MX-fp8 scoring forward) | "
                         "mlp-fp8-train (mlp-fp8 plus the MX-fp8 training "
-                        "forward)")
+                        "forward) | mlp-fp8-train-bwd (mlp-fp8-train plus "
+                        "the MX-fp8 backward GEMMs, e5m2 gradients)")
     p.add_argument("--device", default=None)
     p.add_argument("--start-date", default="2026-01-01")
     p.add_argument("--format", default="csv", choices=["csv", "npy"])

@@ -3,7 +3,9 @@
 `--check` validates layout/scale semantics EXACTLY with integer-valued
 operands (every value e4m3-representable, dot products exact in fp32) and
 measures quantisation accuracy on random data; `--bench` prints TFLOP/s
-on the hot shapes next to the bf16 8-phase kernel for the A/B.
+on the hot shapes next to the bf16 8-phase kernel for the A/B;
+`--bench-train` / `--bench-bwd` time the fp8 training forward's and
+backward's kernels against the bf16 calls they replace.
 """
 import argparse
 import os
@@ -168,6 +170,70 @@ def bench_train_forward(m: int, n: int, k: int) -> None:
           f"net forward saving {(tb - t8 - (td - te)) * 1e3:.3f} ms")
 
 
+def bench_train_backward(m: int, n: int, k: int) -> None:
+    """The fp8 TRAINING backward's kernels against the bf16 calls they
+    replace, at batch m and hidden n == k: dgrad (e5m2 x e4m3, mask-mul
+    epilogue, bf16 out) vs ``linear_bf16(mask=)``; wgrad (two byte
+    transposes + e4m3 x e5m2, fp32 out) vs ``gemm_tn_bf16`` (which
+    includes its two bf16 transposes); the dual-emit expand vs the bf16
+    expand; and the per-step amax kernel."""
+    assert n == k, "the backward GEMMs are H x H: pass MxHxH"
+    g = torch.Generator(device="cuda").manual_seed(3)
+    H = n
+    dy = torch.randn(m, generator=g, device="cuda") * (2.0 / m)
+    w3 = (torch.randn(H, generator=g, device="cuda")
+          * (2.0 / H) ** 0.5).bfloat16()
+    W2t = torch.randn(H, H, generator=g, device="cuda") * (2.0 / H) ** 0.5
+    h1 = torch.randn(m, H, generator=g, device="cuda").relu_()
+    mask1 = torch.randint(0, 256, (m, H // 8), generator=g, device="cuda",
+                          dtype=torch.uint8)
+    mask2 = torch.randint(0, 256, (m, H // 8), generator=g, device="cuda",
+                          dtype=torch.uint8)
+    w2q, e_w2 = _quant(W2t)
+    h1q, e_h1 = _quant(h1)
+    W2t_bf, h1_bf = W2t.bfloat16(), h1.bfloat16()
+    fl = 2.0 * m * H * H
+
+    t_amax = _time_gemm(lambda: ops.amax_exponent_e5m2(dy, w3))
+    e_g = ops.amax_exponent_e5m2(dy, w3)
+    t_ex8 = _time_gemm(lambda: ops.expand1d_bf16_e5m2(dy, w3, mask2, e_g))
+    t_exb = _time_gemm(lambda: ops.expand1d_bf16(dy, w3, None, relu=False,
+                                                 mask=mask2))
+    dz2, dz2q = ops.expand1d_bf16_e5m2(dy, w3, mask2, e_g)
+    print(f"amax_exponent_e5m2 n={m} H={H}: {t_amax * 1e3:.3f} ms")
+    print(f"expand {m}x{H}: bf16+e5m2 dual emit {t_ex8 * 1e3:.3f} ms | "
+          f"bf16 only {t_exb * 1e3:.3f} ms | extra "
+          f"{(t_ex8 - t_exb) * 1e3:.3f} ms")
+
+    t_d8 = _time_gemm(lambda: ops.gemm_mx8_nt_fmt(
+        dz2q, e_g, w2q, e_w2, "e5m2", "e4m3", mask=mask1))
+    t_db = _time_gemm(lambda: ops.linear_bf16(dz2, W2t_bf, mask=mask1))
+    print(f"dgrad {m}x{H}x{H}: gemm_mx8_nt_fmt(e5m2,e4m3,mask) "
+          f"{t_d8 * 1e3:.3f} ms ({fl / t_d8 / 1e12:.0f} TF) | "
+          f"linear_bf16(mask) {t_db * 1e3:.3f} ms "
+          f"({fl / t_db / 1e12:.0f} TF) | ratio {t_db / t_d8:.2f}x")
+
+    t_t1 = _time_gemm(lambda: ops.transpose_u8(h1q))
+    t_t2 = _time_gemm(lambda: ops.transpose_u8(dz2q))
+    h1qt, dz2qt = ops.transpose_u8(h1q), ops.transpose_u8(dz2q)
+    t_w8 = _time_gemm(lambda: ops.gemm_mx8_nt_fmt(
+        h1qt, e_h1, dz2qt, e_g, "e4m3", "e5m2", out_fp32=True))
+    t_wb = _time_gemm(lambda: ops.gemm_tn_bf16(h1_bf, dz2, out_fp32=True))
+    t_tb = _time_gemm(lambda: ops.transpose_bf16(h1_bf))
+    gb = m * H * 2 / 1e9  # bytes read + written by one byte transpose
+    print(f"transpose_u8 {m}x{H}: {t_t1 * 1e3:.3f} ms, {t_t2 * 1e3:.3f} ms "
+          f"({gb / t_t1:.0f} GB/s) | transpose_bf16 {t_tb * 1e3:.3f} ms "
+          f"({2 * gb / t_tb:.0f} GB/s)")
+    t_w8_all = t_w8 + t_t1 + t_t2
+    print(f"wgrad {H}x{H}x{m}: gemm_mx8_nt_fmt(e4m3,e5m2,fp32) "
+          f"{t_w8 * 1e3:.3f} ms ({fl / t_w8 / 1e12:.0f} TF), with its two "
+          f"transposes {t_w8_all * 1e3:.3f} ms | gemm_tn_bf16 (incl. its "
+          f"transposes) {t_wb * 1e3:.3f} ms | ratio {t_wb / t_w8_all:.2f}x")
+    saved = (t_db - t_d8) + (t_wb - t_w8_all) - (t_ex8 - t_exb) - t_amax
+    print(f"net backward saving per step (kernels only, without the second "
+          f"W2 shadow's requantisation): {saved * 1e3:.3f} ms")
+
+
 def main() -> None:
     p = argparse.ArgumentParser()
     p.add_argument("--check", action="store_true")
@@ -175,16 +241,23 @@ def main() -> None:
     p.add_argument("--bench-train", action="store_true",
                    help="time gemm_mx8_relu_mask against "
                         "linear_relu_mask_bf16 at --shape")
+    p.add_argument("--bench-bwd", action="store_true",
+                   help="time the fp8 backward's kernels (dgrad, wgrad + "
+                        "byte transposes, dual-emit expand, amax) against "
+                        "the bf16 calls they replace at --shape")
     p.add_argument("--shape", default="65536x4096x4096",
-                   help="MxNxK for --bench-train")
+                   help="MxNxK for --bench-train / --bench-bwd")
     args = p.parse_args()
     rc = 0
-    if args.check or not (args.bench or args.bench_train):
+    if args.check or not (args.bench or args.bench_train
+                          or args.bench_bwd):
         rc = check()
     if args.bench:
         bench()
     if args.bench_train:
         bench_train_forward(*(int(v) for v in args.shape.split("x")))
+    if args.bench_bwd:
+        bench_train_backward(*(int(v) for v in args.shape.split("x")))
     raise SystemExit(rc)
 
 
