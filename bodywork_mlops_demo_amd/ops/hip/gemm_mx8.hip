@@ -1,12 +1,6 @@
 // MX-FP8 (e4m3 / e5m2) 256x256-tile NT GEMM for gfx950 — the 2x-rate
-// low-precision path.  TWO schedules live here:
-//   - gemm_mx8_nt_1p_kernel (DEFAULT): single-phase-per-tile, 1 barrier
-//     per K-tile, B triple-buffered into the full 160 KB LDS — PMC
-//     shows −20% wave cycles vs the 2-phase schedule at identical MFMA
-//     work, measured +6-10% on every shape (profiles/r02_mx8_1p.md);
-//   - gemm_mx8_nt_kernel: the original 2-phase port of gemm8.hip's
-//     8-phase structure (BODYWORK_MX_1P=0), kept as the reference
-//     schedule and for the supertile/XCD remap experiments.
+// low-precision path.  ONE schedule: gemm_mx8_nt_1p_kernel, a single
+// phase and a single barrier per K-tile.
 //
 // Why this shape: the non-scaled fp8 MFMAs (mfma_f32_16x16x32_fp8_fp8)
 // run at the BF16 rate on CDNA4 — the ONLY 2x-rate fp8 instruction is
@@ -15,19 +9,41 @@
 // feeds it PER-TENSOR power-of-two scales: every lane passes the same
 // E8M0 byte (the tensor's shared exponent), so the hardware dequant does
 // the rescale for free and there is ZERO scale memory traffic in the
-// K-loop — which lets the kernel keep gemm8.hip's proven 16-wave 8-phase
-// structure completely unchanged in its memory system:
+// K-loop.
 //
-//   BK = 128 fp8 bytes/row  ==  gemm8's BK=64 bf16 bytes/row (128 B)
-//   -> identical half-tile size (16 KiB), identical glds schedule,
-//      identical vmcnt(2)/vmcnt(0) landing proofs, identical XOR swizzle
-//      (8 x 16-B chunks per row), identical barrier structure.
+// Geometry: 16 waves (4x4) per 1024-thread block, 64x64 of C per wave =
+// 4x4 fragments.  BK = 128 fp8 bytes/row == gemm8.hip's BK=64 bf16
+// (128 B/row), so a half-tile is the same 16 KiB and is staged the same
+// way: ONE wave-level global_load_lds per wave per half-tile, the XOR
+// swizzle carried on the glds SOURCE address.  One K-tile is ONE K=128
+// MFMA per output fragment (vs four K=32 bf16 MFMAs); each lane's A/B
+// fragment is 32 consecutive k bytes (two adjacent ds_read_b128).
 //
-// What changes: one K-tile is ONE K=128 MFMA per output fragment (vs
-// four K=32 bf16 MFMAs), each lane's A/B fragment is 32 consecutive k
-// bytes = chunks {2*kg, 2*kg+1} (two ds_read_b128), and the MFMA count
-// per phase halves while each MFMA is 4x the work -> the schedule gets
-// MORE compute per staged byte, i.e. deeper latency hiding than bf16.
+// Schedule: A is double-buffered, B TRIPLE-buffered (LDS = 2x32 + 3x32 =
+// 160 KB, the full CU), which is what lets one barrier per K-tile keep
+// every overwrite barrier-separated.  Per tile T (slots: A T%2, B T%3):
+//
+//   wait vmcnt(2) [vmcnt(0) on the last tile]; barrier
+//   issue A(T+1) -> slot (T+1)%2   [overwrites A(T-1), read last phase]
+//   issue B(T+2) -> slot (T+2)%3   [overwrites B(T-1), read last phase]
+//   read B(T) x4 frags + A mfrag 0,1; 8 MFMAs; read A mfrag 2,3; 8 MFMAs
+//
+// Landing proof: per phase the issue order is [A(T+1), B(T+2)], so at
+// wait(T) the 2 newest outstanding glds are B(T+1)'s halves (issued at
+// phase T-1 after A(T)) — vmcnt(2) proves A(T) and everything older
+// (incl. B(T), issued at phase T-2) landed.  Near the end the guarded
+// issues only SHRINK the outstanding set, and the final tile waits
+// vmcnt(0).  Slot safety: both overwrites target buffers whose reads
+// were consumed by the PREVIOUS phase's MFMAs, before this phase's
+// barrier.
+//
+// History: the first version was a 2-phase port of gemm8.hip's schedule
+// (two barriers per K-tile, 128 KB LDS) with optional supertile / XCD
+// block remaps.  This schedule beat it by 6-10% on every shape at
+// identical MFMA work (−20% wave cycles, profiles/r02_mx8_1p.md) and the
+// remaps stayed within noise of the natural dispatch order
+// (profiles/r02_mx8_pmc.md), so both were removed; they are in the
+// history at commit 850e461.
 //
 // Numerics: A and B are e4m3 with per-tensor shared exponents ea, eb
 // (value = 2^e * stored).  Scale operands sa = ea+127, sb = eb+127
@@ -198,201 +214,6 @@ __device__ __forceinline__ void mx_epilogue(
   }
 }
 
-template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false,
-          int AFMT = MX_FMT_E4M3, int BFMT = MX_FMT_E4M3,
-          bool DEV_SCALE = false>
-__launch_bounds__(MX_THREADS)
-__global__ void gemm_mx8_nt_kernel(
-    const unsigned char* __restrict__ A,  // [M,K] fp8 (AFMT), row-major
-    const unsigned char* __restrict__ B,  // [N,K] fp8 (BFMT), row-major
-    const float* __restrict__ bias, const float* __restrict__ w3,
-    unsigned char* __restrict__ mask_out, void* __restrict__ C, long long M,
-    long long N, long long K, int sa, int sb,
-    int super,      // supertile height in y-blocks (sa/sb: E8M0 bytes)
-    int xcd_aware,
-    const int* __restrict__ ea_dev = nullptr,  // DEV_SCALE only
-    const int* __restrict__ eb_dev = nullptr,
-    const unsigned char* __restrict__ mask_in = nullptr) {  // MASK_MUL only
-  __shared__ char lds[8 * MX_HTB];  // ONE __shared__ object (guide trap (a))
-  mx_dev_scales<DEV_SCALE>(sa, sb, ea_dev, eb_dev);
-  // Supertile blockIdx remap (super > 1): consecutive dispatch ids walk
-  // an (x-cols x super-rows) PATCH instead of a full grid-x row, so the
-  // ~256 concurrently-resident workgroups (1 block/CU) touch
-  // super x 1 MB of A + (concurrent/super) x 1 MB of B instead of
-  // re-streaming all of B per grid-y row.  At M=65536, N=K=4096 the
-  // x-major order reads ~8 GB of tiles per launch (= 7.5 TB/s at the
-  // measured rate — HBM-saturated); a square patch cuts that ~4-8x.
-  int bx = blockIdx.x, by = blockIdx.y;
-  if (super > 1) {
-    int linear = blockIdx.x + blockIdx.y * gridDim.x;
-    // XCD-aware transpose (env BODYWORK_MX_XCD=0 disables): dispatch
-    // round-robins workgroups across the 8 XCDs (block i -> XCD i%8),
-    // each with its OWN L2 — a naive patch spreads over 8 disjoint
-    // L2s.  Mapping i -> (i%8)*(G/8) + i/8 gives each XCD a CONTIGUOUS
-    // run of the supertile order, i.e. a compact sub-patch resident in
-    // ITS L2 (guide: +10-12% when HBM-bound).
-    const int G = (int)(gridDim.x * gridDim.y);
-    if (xcd_aware && G % 8 == 0)
-      linear = (linear % 8) * (G / 8) + (linear / 8);
-    int band_sz = super * gridDim.x;
-    int band = linear / band_sz;
-    int in_band = linear % band_sz;
-    int gy = min(super, (int)gridDim.y - band * super);
-    bx = in_band / gy;
-    by = band * super + in_band % gy;
-  }
-  const long long m0 = (long long)by * MX_BM;
-  const long long n0 = (long long)bx * MX_BN;
-  const int wave = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const int wm = wave >> 2;  // 0..3 (64 C-rows per wave)
-  const int wn = wave & 3;   // 0..3 (64 C-cols per wave)
-  const int fl = lane & 15;
-  const int kg = lane >> 4;
-  // XOR swizzle at 32-BYTE granularity — the fp8 fragment size, so a
-  // fragment is two ADJACENT b128 reads (chunk32 c of row r lives at
-  // (c ^ (r & 3)) * 32).  Measured equivalent to the 16-B-chunk
-  // stride-2 variant: SQ_LDS_BANK_CONFLICT reads exactly 4 events per
-  // v_mfma_scale under BOTH layouts (6.711e8 = 4x the MFMA count,
-  // unchanged by the swizzle change) — an artifact of the scaled-MFMA
-  // instruction, not real ds_read serialisation
-  // (profiles/r02_mx8_pmc.md).
-  const int swz = fl & 3;
-  const long long nt = K / MX_BK;
-
-#define MX_ASLOT(buf, half) (lds + ((buf) * 2 + (half)) * MX_HTB)
-#define MX_BSLOT(buf, half) (lds + 4 * MX_HTB + ((buf) * 2 + (half)) * MX_HTB)
-
-  const int a_inhalf = (wm & 1) * 64;
-  const int b_inhalf = (wn & 1) * 64;
-
-  mx_f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
-
-  // one fragment = 32 consecutive k bytes = LDS chunks {2kg, 2kg+1}
-  // (XOR-swizzled), read as two b128s straight into the halves of the
-  // i32x8 MFMA operand (a per-element insertelement assembly costs ~5
-  // v_mov per fragment — 304 v_movs per unrolled loop, measured in the
-  // .s — so the loads are written through a union to land in the
-  // operand's own register quadruples)
-#define MX_READ8(dst, rowbase, rowoff)                                      \
-  do {                                                                      \
-    const char* _rb = (rowbase) + (rowoff) * 128 + ((kg ^ swz) * 32);       \
-    ((mx_i32x4*)&(dst))[0] = *(const mx_i32x4*)(_rb);                       \
-    ((mx_i32x4*)&(dst))[1] = *(const mx_i32x4*)(_rb + 16);                  \
-  } while (0)
-
-#define MX_AREAD(dst, buf, mfrag)                                           \
-  MX_READ8(dst, MX_ASLOT(buf, (wm >> 1)), a_inhalf + (mfrag) * 16 + fl)
-#define MX_BREAD(dst, buf, nfrag)                                           \
-  MX_READ8(dst, MX_BSLOT(buf, (wn >> 1)), b_inhalf + (nfrag) * 16 + fl)
-
-  mx_i32x8 a_q[2];     // this phase's two A fragments (mfrag pair)
-  mx_i32x8 b_t[4];     // current tile's B fragments [nfrag]
-
-  // per-lane staging byte offset (tile-invariant): thread ci stages the
-  // 16-B half `ci&1` of 32-B chunk `(ci&7)>>1` of row `ci>>3`; the
-  // 32-B chunk lands at (chunk ^ (row & 3)) * 32 in LDS, halves stay
-  // adjacent, so the glds SOURCE address carries the swizzle exactly as
-  // in the bf16 kernel
-  int stg_off;
-  {
-    int ci = (int)threadIdx.x;
-    int row = ci >> 3;
-    int c32 = ((ci & 7) >> 1) ^ (row & 3);
-    stg_off = (int)(row * K + (c32 * 32 + (ci & 1) * 16));
-  }
-  const char* Ah0 = (const char*)(A + m0 * K);
-  const char* Ah1 = (const char*)(A + (m0 + 128) * K);
-  const char* Bh0 = (const char*)(B + n0 * K);
-  const char* Bh1 = (const char*)(B + (n0 + 128) * K);
-#define MX_KOFF(T) ((long long)(T) * MX_BK)
-
-  // prologue: A(0), B(0), B(1) — A(1) is issued by the loop at (0,A)
-  mx_stage_half(MX_ASLOT(0, 0), Ah0, stg_off);
-  mx_stage_half(MX_ASLOT(0, 1), Ah1, stg_off);
-  mx_stage_half(MX_BSLOT(0, 0), Bh0, stg_off);
-  mx_stage_half(MX_BSLOT(0, 1), Bh1, stg_off);
-  if (nt > 1) {
-    mx_stage_half(MX_BSLOT(1, 0), Bh0 + MX_KOFF(1), stg_off);
-    mx_stage_half(MX_BSLOT(1, 1), Bh1 + MX_KOFF(1), stg_off);
-  }
-
-  // Two phases per K-tile, one barrier each — gemm8's v4 schedule with
-  // identical glds issue order, so the same landing proof holds: at
-  // wait(T,A) the newest 2 outstanding glds are B(T+1)'s halves, the
-  // 3rd/4th-newest are A(T)'s -> vmcnt(2) proves tile T landed; the
-  // last tile drains with vmcnt(0).  Slot safety: A(T+1) overwrites
-  // A(T-1) whose mfrag2/3 reads were consumed before barrier(T,A);
-  // B(T+2) overwrites B(T), consumed before barrier(T,B).
-#define MX_MFMA(acc_i, afrag)                                               \
-  _Pragma("unroll") for (int nf = 0; nf < 4; ++nf)                          \
-      acc[acc_i][nf] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(    \
-          afrag, b_t[nf], acc[acc_i][nf], AFMT, BFMT, 0, sa, 0, sb)
-
-#define MX_PHASE_A(T, TPAR)                                                 \
-  do {                                                                      \
-    if ((T) + 1 < nt)                                                       \
-      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");                      \
-    else                                                                    \
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                      \
-    __builtin_amdgcn_s_barrier();                                           \
-    if ((T) + 1 < nt) {                                                     \
-      mx_stage_half(MX_ASLOT(1 - (TPAR), 0), Ah0 + MX_KOFF((T) + 1),        \
-                    stg_off);                                               \
-      mx_stage_half(MX_ASLOT(1 - (TPAR), 1), Ah1 + MX_KOFF((T) + 1),        \
-                    stg_off);                                               \
-    }                                                                       \
-    _Pragma("unroll") for (int nf = 0; nf < 4; ++nf)                        \
-        MX_BREAD(b_t[nf], TPAR, nf);                                        \
-    MX_AREAD(a_q[0], TPAR, 0);                                              \
-    MX_AREAD(a_q[1], TPAR, 1);                                              \
-    __builtin_amdgcn_s_setprio(1);                                          \
-    MX_MFMA(0, a_q[0]);                                                     \
-    MX_MFMA(1, a_q[1]);                                                     \
-    __builtin_amdgcn_s_setprio(0);                                          \
-  } while (0)
-
-#define MX_PHASE_B(T, TPAR)                                                 \
-  do {                                                                      \
-    __builtin_amdgcn_s_barrier();                                           \
-    if ((T) + 2 < nt) {                                                     \
-      mx_stage_half(MX_BSLOT(TPAR, 0), Bh0 + MX_KOFF((T) + 2), stg_off);    \
-      mx_stage_half(MX_BSLOT(TPAR, 1), Bh1 + MX_KOFF((T) + 2), stg_off);    \
-    }                                                                       \
-    MX_AREAD(a_q[0], TPAR, 2);                                              \
-    MX_AREAD(a_q[1], TPAR, 3);                                              \
-    __builtin_amdgcn_s_setprio(1);                                          \
-    MX_MFMA(2, a_q[0]);                                                     \
-    MX_MFMA(3, a_q[1]);                                                     \
-    __builtin_amdgcn_s_setprio(0);                                          \
-  } while (0)
-
-  // two tiles per iteration: buffer indices stay compile-time
-  for (long long t = 0; t < nt; t += 2) {
-    MX_PHASE_A(t, 0);
-    MX_PHASE_B(t, 0);
-    if (t + 1 < nt) {
-      MX_PHASE_A(t + 1, 1);
-      MX_PHASE_B(t + 1, 1);
-    }
-  }
-#undef MX_PHASE_A
-#undef MX_PHASE_B
-#undef MX_MFMA
-#undef MX_AREAD
-#undef MX_BREAD
-#undef MX_READ8
-#undef MX_ASLOT
-#undef MX_BSLOT
-
-  mx_epilogue<EPI, HAS_BIAS, OUT_FP32, EMIT_MASK>(
-      acc, bias, w3, mask_out, C, M, N, m0, n0, wm, wn, fl, kg, mask_in);
-}
-
 // ---- per-tensor e4m3 quantisation ----------------------------------------
 //
 // x (bf16 or fp32) -> e4m3 bytes, value = 2^e * stored.  e is chosen
@@ -428,29 +249,12 @@ __global__ void quantize_e4m3_kernel(const T* __restrict__ x,
   }
 }
 
-// ---- single-phase-per-tile variant (env BODYWORK_MX_1P=1) -----------------
+// ---- the MX GEMM kernel: one phase, one barrier per K-tile -----------------
 //
-// ONE barrier per K-tile instead of two: A stays double-buffered, B
-// goes TRIPLE-buffered (LDS = 2x32 + 3x32 = 160 KB, the full CU), so
-// every overwrite stays barrier-separated with half the barrier count
-// per MFMA.  Schedule per tile T (slots: A T%2, B T%3; 6-phase unroll
-// so every slot index is compile-time):
-//
-//   wait vmcnt(2) [vmcnt(0) on the last tile]; barrier
-//   issue A(T+1) -> slot (T+1)%2   [overwrites A(T-1), read last phase]
-//   issue B(T+2) -> slot (T+2)%3   [overwrites B(T-1), read last phase]
-//   read B(T) x4 frags + A mfrag 0,1; 8 MFMAs; read A mfrag 2,3; 8 MFMAs
-//
-// Landing proof: per phase the issue order is [A(T+1), B(T+2)], so at
-// wait(T) the 2 newest outstanding glds are B(T+1)'s halves (issued at
-// phase T-1 after A(T)) — vmcnt(2) proves A(T) and everything older
-// (incl. B(T), issued at phase T-2) landed.  Near the end the guarded
-// issues only SHRINK the outstanding set, and the final tile waits
-// vmcnt(0).  Slot safety: both overwrites target buffers whose reads
-// were consumed by the PREVIOUS phase's MFMAs, before this phase's
-// barrier.
+// Schedule and landing proof: see the file header.
 #define P1_ASLOT(buf, half) (lds + ((buf) * 2 + (half)) * MX_HTB)
 #define P1_BSLOT(buf, half) (lds + (4 + (buf) * 2 + (half)) * MX_HTB)
+#define MX_KOFF(T) ((long long)(T) * MX_BK)  // byte offset of K-tile T in a row
 
 template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false,
           int AFMT = MX_FMT_E4M3, int BFMT = MX_FMT_E4M3,
@@ -474,6 +278,14 @@ __global__ void gemm_mx8_nt_1p_kernel(
   const int wn = wave & 3;
   const int fl = lane & 15;
   const int kg = lane >> 4;
+  // XOR swizzle at 32-BYTE granularity — the fp8 fragment size, so a
+  // fragment is two ADJACENT b128 reads (chunk32 c of row r lives at
+  // (c ^ (r & 3)) * 32).  Measured equivalent to the 16-B-chunk
+  // stride-2 variant: SQ_LDS_BANK_CONFLICT reads exactly 4 events per
+  // v_mfma_scale under BOTH layouts (6.711e8 = 4x the MFMA count,
+  // unchanged by the swizzle change) — an artifact of the scaled-MFMA
+  // instruction, not real ds_read serialisation
+  // (profiles/r02_mx8_pmc.md).
   const int swz = fl & 3;
   const int nt = (int)(K / MX_BK);
   const int a_inhalf = (wm & 1) * 64;
@@ -499,6 +311,12 @@ __global__ void gemm_mx8_nt_1p_kernel(
 #define P1_AR_BASE(slotp) ((slotp) + (wm >> 1) * MX_HTB)
 #define P1_BR_BASE(slotp) ((slotp) + (wn >> 1) * MX_HTB)
 
+  // one fragment = 32 consecutive k bytes = LDS chunks {2kg, 2kg+1}
+  // (XOR-swizzled), read as two b128s straight into the halves of the
+  // i32x8 MFMA operand (a per-element insertelement assembly costs ~5
+  // v_mov per fragment — 304 v_movs per unrolled loop, measured in the
+  // .s — so the loads are written through the operand's i32x4 halves
+  // to land in its own register quadruples)
 #define P1_READ8(dst, rowbase, rowoff)                                      \
   do {                                                                      \
     const char* _rb = (rowbase) + (rowoff) * 128 + ((kg ^ swz) * 32);       \
@@ -509,6 +327,11 @@ __global__ void gemm_mx8_nt_1p_kernel(
   mx_i32x8 a_q[2];
   mx_i32x8 b_t[4];
 
+  // per-lane staging byte offset (tile-invariant): thread ci stages the
+  // 16-B half `ci&1` of 32-B chunk `(ci&7)>>1` of row `ci>>3`; the
+  // 32-B chunk lands at (chunk ^ (row & 3)) * 32 in LDS, halves stay
+  // adjacent, so the glds SOURCE address carries the swizzle exactly as
+  // in the bf16 kernel
   int stg_off;
   {
     int ci = (int)threadIdx.x;
@@ -873,43 +696,6 @@ __global__ void transpose_u8_kernel(const unsigned char* __restrict__ src,
 
 // ---- host wrappers --------------------------------------------------------
 
-// supertile height (y-blocks) for the blockIdx remap; latched once.
-// DEFAULT 1 (identity): the A/B matrix across supertile heights and
-// the XCD transpose measured within +-2-4% of the natural dispatch
-// order on every shape (profiles/r02_mx8_pmc.md) — L2 + dispatch
-// overlap already cover the tile re-streaming, so the least machinery
-// stays in play.  Envs kept for future A/B on other shapes.
-static int mx_supertile() {
-  static int v = [] {
-    const char* e = getenv("BODYWORK_MX_SUPER");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
-
-static int mx_xcd_aware() {
-  static int v = [] {
-    const char* e = getenv("BODYWORK_MX_XCD");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
-
-// single-phase-per-tile variant (1 barrier/K-tile, B triple-buffered,
-// 160 KB LDS).  DEFAULT since its hardware A/B won on every shape
-// (+6-10%: 2042/2412/2186 TF vs 1920/2194/1998 same box) with the full
-// test file green normally AND under AMD_SERIALIZE_KERNEL/COPY,
-// bitwise-repeatable over 20 replays, exact at odd/clamp shapes
-// (profiles/r02_mx8_1p.md).  BODYWORK_MX_1P=0 reverts to the 2-phase
-// kernel.
-static int mx_one_phase() {
-  static int v = [] {
-    const char* e = getenv("BODYWORK_MX_1P");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
-
 at::Tensor expand1d_e4m3_hip(const at::Tensor& x, const at::Tensor& w,
                              const c10::optional<at::Tensor>& b,
                              int64_t e) {
@@ -1004,65 +790,110 @@ at::Tensor quantize_e4m3_hip(const at::Tensor& x, int64_t e) {
   return out;
 }
 
+// ---- MX GEMM ops: one operand check, one launcher --------------------------
+
+// Everything a gemm_mx8_nt_1p_kernel launch takes.  mx_gemm_operands
+// fills the problem and the operand pointers; each op sets the scales and
+// the epilogue pointers it uses and leaves the rest null.
+struct MxGemm {
+  long long M = 0, N = 0, K = 0;
+  dim3 grid;
+  const unsigned char* a = nullptr;
+  const unsigned char* b = nullptr;
+  int sa = 127, sb = 127;             // E8M0 bytes (host part)
+  const int* ea_dev = nullptr;        // DEV_SCALE
+  const int* eb_dev = nullptr;
+  const float* bias = nullptr;        // BIAS_RELU / RELU_DOT
+  const float* w3 = nullptr;          // RELU_DOT
+  unsigned char* mask_out = nullptr;  // EMIT_MASK
+  const unsigned char* mask_in = nullptr;  // MASK_MUL
+  void* c = nullptr;
+  bool empty() const { return M == 0 || N == 0; }  // nothing to launch
+};
+
+// The operand pair every MX GEMM op takes: a8 [M,K] and b8 [N,K] fp8
+// bytes.  `op` prefixes the error texts.
+static MxGemm mx_gemm_operands(const char* op, const at::Tensor& a8,
+                               const at::Tensor& b8) {
+  TORCH_CHECK(a8.is_cuda() && b8.is_cuda(), op, ": cuda tensors");
+  TORCH_CHECK(a8.scalar_type() == torch::kUInt8 &&
+                  b8.scalar_type() == torch::kUInt8,
+              op, ": fp8 byte tensors");
+  TORCH_CHECK(a8.dim() == 2 && b8.dim() == 2 && a8.size(1) == b8.size(1),
+              op, ": [M,K]x[N,K]");
+  TORCH_CHECK(a8.is_contiguous() && b8.is_contiguous(), op,
+              ": operands must be contiguous");
+  MxGemm g;
+  g.M = a8.size(0), g.K = a8.size(1), g.N = b8.size(0);
+  TORCH_CHECK(g.M % MX_BM == 0 && g.N % MX_BN == 0 && g.K % MX_BK == 0, op,
+              " requires M%256==0, N%256==0, K%128==0 (got ", g.M, "x", g.N,
+              "x", g.K, ")");
+  TORCH_CHECK((uintptr_t)a8.data_ptr() % 16 == 0 &&
+                  (uintptr_t)b8.data_ptr() % 16 == 0,
+              op, ": operands must be 16-byte aligned");
+  g.grid = dim3((unsigned)(g.N / MX_BN), (unsigned)(g.M / MX_BM));
+  g.a = a8.data_ptr<unsigned char>();
+  g.b = b8.data_ptr<unsigned char>();
+  return g;
+}
+
+// host exponent -> E8M0 byte; out-of-range stays loud
+static int mx_e8m0(const char* op, int64_t e) {
+  TORCH_CHECK(-127 <= e && e <= 127, op,
+              ": per-tensor exponent out of E8M0 range");
+  return (int)e + 127;
+}
+
+// optional fp32 [N] epilogue vector (bias, b2, w3) -> pointer, nullptr
+// when absent
+static const float* mx_vec_n(const char* op, const char* what,
+                             const c10::optional<at::Tensor>& v,
+                             long long N) {
+  if (!v.has_value() || !v->defined()) return nullptr;
+  TORCH_CHECK(v->is_cuda() && v->scalar_type() == torch::kFloat &&
+                  v->numel() == N && v->is_contiguous(),
+              op, ": ", what, " must be a contiguous fp32 [N] cuda tensor");
+  return v->data_ptr<float>();
+}
+
+template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false,
+          int AFMT = MX_FMT_E4M3, int BFMT = MX_FMT_E4M3,
+          bool DEV_SCALE = false>
+static void mx_launch(const MxGemm& g) {
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  hipLaunchKernelGGL((gemm_mx8_nt_1p_kernel<EPI, HAS_BIAS, OUT_FP32, EMIT_MASK,
+                                            AFMT, BFMT, DEV_SCALE>),
+                     g.grid, dim3(MX_THREADS), 0, stream, g.a, g.b, g.bias,
+                     g.w3, g.mask_out, g.c, g.M, g.N, g.K, g.sa, g.sb,
+                     g.ea_dev, g.eb_dev, g.mask_in);
+}
+
 // C[M,N] = 2^(ea+eb) * (A[M,K]e4m3 . B[N,K]e4m3^T), optional fused
 // bias+relu epilogue, fp32 or bf16 output.
 at::Tensor gemm_mx8_nt_hip(const at::Tensor& a8, int64_t ea,
                            const at::Tensor& b8, int64_t eb,
                            const c10::optional<at::Tensor>& bias, bool relu,
                            bool out_fp32) {
-  TORCH_CHECK(a8.is_cuda() && b8.is_cuda(), "gemm_mx8_nt: cuda tensors");
-  TORCH_CHECK(a8.scalar_type() == torch::kUInt8 &&
-                  b8.scalar_type() == torch::kUInt8,
-              "gemm_mx8_nt: e4m3 byte tensors");
-  TORCH_CHECK(a8.dim() == 2 && b8.dim() == 2 && a8.size(1) == b8.size(1),
-              "gemm_mx8_nt: [M,K]x[N,K]");
-  TORCH_CHECK(a8.is_contiguous() && b8.is_contiguous(), "contiguous");
-  long long M = a8.size(0), K = a8.size(1), N = b8.size(0);
-  TORCH_CHECK(M % MX_BM == 0 && N % MX_BN == 0 && K % MX_BK == 0,
-              "gemm_mx8_nt requires M%256==0, N%256==0, K%128==0 (got ", M,
-              "x", N, "x", K, ")");
-  int sa = (int)std::min<long long>(std::max<long long>(ea + 127, 0), 254);
-  int sb = (int)std::min<long long>(std::max<long long>(eb + 127, 0), 254);
-  TORCH_CHECK(sa == ea + 127 && sb == eb + 127,
-              "per-tensor exponent out of E8M0 range");
+  const char* op = "gemm_mx8_nt";
+  MxGemm g = mx_gemm_operands(op, a8, b8);
+  g.sa = mx_e8m0(op, ea);
+  g.sb = mx_e8m0(op, eb);
+  g.bias = mx_vec_n(op, "bias", bias, g.N);
+  TORCH_CHECK(relu || !g.bias, op, ": bias requires relu epilogue for now");
   auto opts = a8.options().dtype(out_fp32 ? torch::kFloat : torch::kBFloat16);
-  auto C = torch::empty({M, N}, opts);
-  const float* bias_p = nullptr;
-  bool has_bias = false;
-  if (bias.has_value() && bias->defined()) {
-    TORCH_CHECK(bias->is_cuda() && bias->scalar_type() == torch::kFloat &&
-                    bias->numel() == N,
-                "bias: fp32 [N] cuda");
-    bias_p = bias->data_ptr<float>();
-    has_bias = true;
-  }
-  dim3 grid((unsigned)(N / MX_BN), (unsigned)(M / MX_BM));
-  auto stream = at::cuda::getCurrentCUDAStream();
-  const unsigned char* ap = a8.data_ptr<unsigned char>();
-  const unsigned char* bp = b8.data_ptr<unsigned char>();
-#define LMX(EPI_, HB_, OF_)                                                 \
-  do {                                                                      \
-    if (mx_one_phase())                                                     \
-      hipLaunchKernelGGL((gemm_mx8_nt_1p_kernel<EPI_, HB_, OF_>), grid,     \
-                         dim3(MX_THREADS), 0, stream, ap, bp, bias_p,       \
-                         nullptr, nullptr, C.data_ptr(), M, N, K, sa, sb);  \
-    else                                                                    \
-      hipLaunchKernelGGL((gemm_mx8_nt_kernel<EPI_, HB_, OF_>), grid,        \
-                         dim3(MX_THREADS), 0, stream, ap, bp, bias_p,       \
-                         nullptr, nullptr, C.data_ptr(), M, N, K, sa, sb,   \
-                         mx_supertile(), mx_xcd_aware());                   \
-  } while (0)
-  if (relu) {
-    if (has_bias) { if (out_fp32) LMX(MX_EPI_BIAS_RELU, true, true);
-                    else          LMX(MX_EPI_BIAS_RELU, true, false); }
-    else          { if (out_fp32) LMX(MX_EPI_BIAS_RELU, false, true);
-                    else          LMX(MX_EPI_BIAS_RELU, false, false); }
+  auto C = torch::empty({g.M, g.N}, opts);
+  if (g.empty()) return C;
+  g.c = C.data_ptr();
+  if (!relu) {
+    if (out_fp32) mx_launch<MX_EPI_NONE, false, true>(g);
+    else          mx_launch<MX_EPI_NONE, false, false>(g);
+  } else if (g.bias) {
+    if (out_fp32) mx_launch<MX_EPI_BIAS_RELU, true, true>(g);
+    else          mx_launch<MX_EPI_BIAS_RELU, true, false>(g);
   } else {
-    TORCH_CHECK(!has_bias, "bias requires relu epilogue for now");
-    if (out_fp32) LMX(MX_EPI_NONE, false, true);
-    else          LMX(MX_EPI_NONE, false, false);
+    if (out_fp32) mx_launch<MX_EPI_BIAS_RELU, false, true>(g);
+    else          mx_launch<MX_EPI_BIAS_RELU, false, false>(g);
   }
-#undef LMX
   return C;
 }
 
@@ -1073,39 +904,17 @@ at::Tensor gemm_mx8_relu_dot_hip(const at::Tensor& a8, int64_t ea,
                                  const at::Tensor& b8, int64_t eb,
                                  const at::Tensor& b2,
                                  const at::Tensor& w3) {
-  TORCH_CHECK(a8.is_cuda() && b8.is_cuda() && a8.dim() == 2 &&
-                  b8.dim() == 2 && a8.size(1) == b8.size(1),
-              "gemm_mx8_relu_dot: [M,K]x[N,K] cuda");
-  TORCH_CHECK(a8.scalar_type() == torch::kUInt8 &&
-              b8.scalar_type() == torch::kUInt8);
-  TORCH_CHECK(a8.is_contiguous() && b8.is_contiguous());
-  long long M = a8.size(0), K = a8.size(1), N = b8.size(0);
-  TORCH_CHECK(M % MX_BM == 0 && N % MX_BN == 0 && K % MX_BK == 0,
-              "gemm_mx8_relu_dot requires M%256==0, N%256==0, K%128==0");
-  TORCH_CHECK(b2.is_cuda() && b2.scalar_type() == torch::kFloat &&
-                  b2.numel() == N, "b2: fp32 [N]");
-  TORCH_CHECK(w3.is_cuda() && w3.scalar_type() == torch::kFloat &&
-                  w3.numel() == N, "w3: fp32 [N]");
-  int sa = (int)(ea + 127), sb = (int)(eb + 127);
-  TORCH_CHECK(0 <= sa && sa <= 254 && 0 <= sb && sb <= 254,
-              "exponent out of E8M0 range");
-  auto y = torch::zeros({M}, a8.options().dtype(torch::kFloat));
-  dim3 grid((unsigned)(N / MX_BN), (unsigned)(M / MX_BM));
-  auto stream = at::cuda::getCurrentCUDAStream();
-  if (mx_one_phase())
-    hipLaunchKernelGGL((gemm_mx8_nt_1p_kernel<MX_EPI_RELU_DOT, true, true>),
-                       grid, dim3(MX_THREADS), 0, stream,
-                       a8.data_ptr<unsigned char>(),
-                       b8.data_ptr<unsigned char>(), b2.data_ptr<float>(),
-                       w3.data_ptr<float>(), nullptr, y.data_ptr(), M, N, K,
-                       sa, sb);
-  else
-    hipLaunchKernelGGL((gemm_mx8_nt_kernel<MX_EPI_RELU_DOT, true, true>),
-                       grid, dim3(MX_THREADS), 0, stream,
-                       a8.data_ptr<unsigned char>(),
-                       b8.data_ptr<unsigned char>(), b2.data_ptr<float>(),
-                       w3.data_ptr<float>(), nullptr, y.data_ptr(), M, N, K,
-                       sa, sb, mx_supertile(), mx_xcd_aware());
+  const char* op = "gemm_mx8_relu_dot";
+  MxGemm g = mx_gemm_operands(op, a8, b8);
+  g.sa = mx_e8m0(op, ea);
+  g.sb = mx_e8m0(op, eb);
+  g.bias = mx_vec_n(op, "b2", b2, g.N);
+  g.w3 = mx_vec_n(op, "w3", w3, g.N);
+  TORCH_CHECK(g.bias && g.w3, op, ": b2 and w3 are required");
+  auto y = torch::zeros({g.M}, a8.options().dtype(torch::kFloat));
+  if (g.empty()) return y;
+  g.c = y.data_ptr();
+  mx_launch<MX_EPI_RELU_DOT, true, true>(g);
   return y;
 }
 
@@ -1116,53 +925,18 @@ at::Tensor gemm_mx8_relu_dot_hip(const at::Tensor& a8, int64_t ea,
 std::tuple<at::Tensor, at::Tensor> gemm_mx8_relu_mask_hip(
     const at::Tensor& a8, int64_t ea, const at::Tensor& b8, int64_t eb,
     const c10::optional<at::Tensor>& bias) {
-  TORCH_CHECK(a8.is_cuda() && b8.is_cuda(), "gemm_mx8_relu_mask: cuda tensors");
-  TORCH_CHECK(a8.scalar_type() == torch::kUInt8 &&
-                  b8.scalar_type() == torch::kUInt8,
-              "gemm_mx8_relu_mask: e4m3 byte tensors");
-  TORCH_CHECK(a8.dim() == 2 && b8.dim() == 2 && a8.size(1) == b8.size(1),
-              "gemm_mx8_relu_mask: [M,K]x[N,K]");
-  TORCH_CHECK(a8.is_contiguous() && b8.is_contiguous(), "contiguous");
-  long long M = a8.size(0), K = a8.size(1), N = b8.size(0);
-  TORCH_CHECK(M % MX_BM == 0 && N % MX_BN == 0 && K % MX_BK == 0,
-              "gemm_mx8_relu_mask requires M%256==0, N%256==0, K%128==0 "
-              "(got ", M, "x", N, "x", K, ")");
-  int sa = (int)(ea + 127), sb = (int)(eb + 127);
-  TORCH_CHECK(0 <= sa && sa <= 254 && 0 <= sb && sb <= 254,
-              "per-tensor exponent out of E8M0 range");
-  auto C = torch::empty({M, N}, a8.options().dtype(torch::kBFloat16));
-  auto mask = torch::empty({M, N / 8}, a8.options());
-  if (M == 0 || N == 0) return {C, mask};
-  const float* bias_p = nullptr;
-  bool has_bias = false;
-  if (bias.has_value() && bias->defined()) {
-    TORCH_CHECK(bias->is_cuda() && bias->scalar_type() == torch::kFloat &&
-                    bias->numel() == N && bias->is_contiguous(),
-                "bias: fp32 [N] cuda");
-    bias_p = bias->data_ptr<float>();
-    has_bias = true;
-  }
-  dim3 grid((unsigned)(N / MX_BN), (unsigned)(M / MX_BM));
-  auto stream = at::cuda::getCurrentCUDAStream();
-  const unsigned char* ap = a8.data_ptr<unsigned char>();
-  const unsigned char* bp = b8.data_ptr<unsigned char>();
-  unsigned char* mp = mask.data_ptr<unsigned char>();
-#define LMXM(HB_)                                                           \
-  do {                                                                      \
-    if (mx_one_phase())                                                     \
-      hipLaunchKernelGGL(                                                   \
-          (gemm_mx8_nt_1p_kernel<MX_EPI_BIAS_RELU, HB_, false, true>),      \
-          grid, dim3(MX_THREADS), 0, stream, ap, bp, bias_p, nullptr, mp,   \
-          C.data_ptr(), M, N, K, sa, sb);                                   \
-    else                                                                    \
-      hipLaunchKernelGGL(                                                   \
-          (gemm_mx8_nt_kernel<MX_EPI_BIAS_RELU, HB_, false, true>), grid,   \
-          dim3(MX_THREADS), 0, stream, ap, bp, bias_p, nullptr, mp,         \
-          C.data_ptr(), M, N, K, sa, sb, mx_supertile(), mx_xcd_aware());   \
-  } while (0)
-  if (has_bias) LMXM(true);
-  else          LMXM(false);
-#undef LMXM
+  const char* op = "gemm_mx8_relu_mask";
+  MxGemm g = mx_gemm_operands(op, a8, b8);
+  g.sa = mx_e8m0(op, ea);
+  g.sb = mx_e8m0(op, eb);
+  g.bias = mx_vec_n(op, "bias", bias, g.N);
+  auto C = torch::empty({g.M, g.N}, a8.options().dtype(torch::kBFloat16));
+  auto mask = torch::empty({g.M, g.N / 8}, a8.options());
+  if (g.empty()) return {C, mask};
+  g.c = C.data_ptr();
+  g.mask_out = mask.data_ptr<unsigned char>();
+  if (g.bias) mx_launch<MX_EPI_BIAS_RELU, true, false, true>(g);
+  else        mx_launch<MX_EPI_BIAS_RELU, false, false, true>(g);
   return {C, mask};
 }
 
@@ -1276,22 +1050,17 @@ at::Tensor transpose_u8_hip(const at::Tensor& src) {
   return dst;
 }
 
-template <int EPI, bool OF, int AF, int BF>
-static void mx_launch_fmt(dim3 grid, hipStream_t stream,
-                          const unsigned char* ap, const unsigned char* bp,
-                          void* cp, long long M, long long N, long long K,
-                          int sa, int sb, const int* eap, const int* ebp,
-                          const unsigned char* mp) {
-  if (mx_one_phase())
-    hipLaunchKernelGGL(
-        (gemm_mx8_nt_1p_kernel<EPI, false, OF, false, AF, BF, true>), grid,
-        dim3(MX_THREADS), 0, stream, ap, bp, nullptr, nullptr, nullptr, cp, M,
-        N, K, sa, sb, eap, ebp, mp);
-  else
-    hipLaunchKernelGGL(
-        (gemm_mx8_nt_kernel<EPI, false, OF, false, AF, BF, true>), grid,
-        dim3(MX_THREADS), 0, stream, ap, bp, nullptr, nullptr, nullptr, cp, M,
-        N, K, sa, sb, mx_supertile(), mx_xcd_aware(), eap, ebp, mp);
+// the four operand-format pairs of one (epilogue, output type)
+template <int EPI, bool OUT_FP32>
+static void mx_launch_fmt(const MxGemm& g, int64_t a_fmt, int64_t b_fmt) {
+  constexpr int E4 = MX_FMT_E4M3, E5 = MX_FMT_E5M2;
+  if (a_fmt == E4) {
+    if (b_fmt == E4) mx_launch<EPI, false, OUT_FP32, false, E4, E4, true>(g);
+    else             mx_launch<EPI, false, OUT_FP32, false, E4, E5, true>(g);
+  } else {
+    if (b_fmt == E4) mx_launch<EPI, false, OUT_FP32, false, E5, E4, true>(g);
+    else             mx_launch<EPI, false, OUT_FP32, false, E5, E5, true>(g);
+  }
 }
 
 // C[M,N] = 2^(ea+eb) * (A[M,K] . B[N,K]^T) [* bit(mask)], A and B each
@@ -1305,65 +1074,35 @@ at::Tensor gemm_mx8_nt_fmt_hip(const at::Tensor& a8, int64_t ea,
                                int64_t a_fmt, int64_t b_fmt,
                                const c10::optional<at::Tensor>& mask,
                                bool out_fp32) {
-  TORCH_CHECK(a8.is_cuda() && b8.is_cuda(), "gemm_mx8_nt_fmt: cuda tensors");
-  TORCH_CHECK(a8.scalar_type() == torch::kUInt8 &&
-                  b8.scalar_type() == torch::kUInt8,
-              "gemm_mx8_nt_fmt: fp8 byte tensors");
-  TORCH_CHECK(a8.dim() == 2 && b8.dim() == 2 && a8.size(1) == b8.size(1),
-              "gemm_mx8_nt_fmt: [M,K]x[N,K]");
-  TORCH_CHECK(a8.is_contiguous() && b8.is_contiguous(), "contiguous");
+  const char* op = "gemm_mx8_nt_fmt";
+  MxGemm g = mx_gemm_operands(op, a8, b8);
   TORCH_CHECK((a_fmt == MX_FMT_E4M3 || a_fmt == MX_FMT_E5M2) &&
                   (b_fmt == MX_FMT_E4M3 || b_fmt == MX_FMT_E5M2),
-              "gemm_mx8_nt_fmt: format must be 0 (e4m3) or 1 (e5m2)");
-  long long M = a8.size(0), K = a8.size(1), N = b8.size(0);
-  TORCH_CHECK(M % MX_BM == 0 && N % MX_BN == 0 && K % MX_BK == 0,
-              "gemm_mx8_nt_fmt requires M%256==0, N%256==0, K%128==0 (got ",
-              M, "x", N, "x", K, ")");
-  TORCH_CHECK((uintptr_t)a8.data_ptr() % 16 == 0 &&
-                  (uintptr_t)b8.data_ptr() % 16 == 0,
-              "gemm_mx8_nt_fmt: operands must be 16-byte aligned");
-  const int* eap = mx_edev_ptr(ea_dev, a8, "gemm_mx8_nt_fmt");
-  const int* ebp = mx_edev_ptr(eb_dev, a8, "gemm_mx8_nt_fmt");
+              op, ": format must be 0 (e4m3) or 1 (e5m2)");
   // host parts stay loud; the device parts are clamped in-kernel
-  TORCH_CHECK(-127 <= ea && ea <= 127 && -127 <= eb && eb <= 127,
-              "per-tensor exponent out of E8M0 range");
-  int sa = (int)ea + 127, sb = (int)eb + 127;
-  const unsigned char* mp = nullptr;
+  g.sa = mx_e8m0(op, ea);
+  g.sb = mx_e8m0(op, eb);
+  g.ea_dev = mx_edev_ptr(ea_dev, a8, op);
+  g.eb_dev = mx_edev_ptr(eb_dev, a8, op);
   if (mask.has_value() && mask->defined()) {
     TORCH_CHECK(mask->is_cuda() && mask->is_contiguous() &&
                     mask->scalar_type() == torch::kUInt8 &&
-                    mask->numel() == M * (N / 8),
-                "gemm_mx8_nt_fmt: mask must be uint8 [M, N/8] bitmask");
-    TORCH_CHECK((uintptr_t)mask->data_ptr() % 8 == 0,
-                "gemm_mx8_nt_fmt: mask must be 8-byte aligned");
-    mp = mask->data_ptr<unsigned char>();
+                    mask->numel() == g.M * (g.N / 8),
+                op, ": mask must be uint8 [M, N/8] bitmask");
+    TORCH_CHECK((uintptr_t)mask->data_ptr() % 8 == 0, op,
+                ": mask must be 8-byte aligned");
+    g.mask_in = mask->data_ptr<unsigned char>();
   }
   auto opts = a8.options().dtype(out_fp32 ? torch::kFloat : torch::kBFloat16);
-  auto C = torch::empty({M, N}, opts);
-  if (M == 0 || N == 0) return C;
-  dim3 grid((unsigned)(N / MX_BN), (unsigned)(M / MX_BM));
-  hipStream_t stream = at::cuda::getCurrentCUDAStream();
-#define LFMT4(EPI_, OF_, AF_, BF_)                                          \
-  mx_launch_fmt<EPI_, OF_, AF_, BF_>(grid, stream,                          \
-                                     a8.data_ptr<unsigned char>(),          \
-                                     b8.data_ptr<unsigned char>(),          \
-                                     C.data_ptr(), M, N, K, sa, sb, eap,    \
-                                     ebp, mp)
-#define LFMT2(EPI_, OF_)                                                    \
-  do {                                                                      \
-    if (a_fmt == MX_FMT_E4M3) {                                             \
-      if (b_fmt == MX_FMT_E4M3) LFMT4(EPI_, OF_, MX_FMT_E4M3, MX_FMT_E4M3); \
-      else                      LFMT4(EPI_, OF_, MX_FMT_E4M3, MX_FMT_E5M2); \
-    } else {                                                                \
-      if (b_fmt == MX_FMT_E4M3) LFMT4(EPI_, OF_, MX_FMT_E5M2, MX_FMT_E4M3); \
-      else                      LFMT4(EPI_, OF_, MX_FMT_E5M2, MX_FMT_E5M2); \
-    }                                                                       \
-  } while (0)
-  if (mp) { if (out_fp32) LFMT2(MX_EPI_MASK_MUL, true);
-            else          LFMT2(MX_EPI_MASK_MUL, false); }
-  else    { if (out_fp32) LFMT2(MX_EPI_NONE, true);
-            else          LFMT2(MX_EPI_NONE, false); }
-#undef LFMT2
-#undef LFMT4
+  auto C = torch::empty({g.M, g.N}, opts);
+  if (g.empty()) return C;
+  g.c = C.data_ptr();
+  if (g.mask_in) {
+    if (out_fp32) mx_launch_fmt<MX_EPI_MASK_MUL, true>(g, a_fmt, b_fmt);
+    else          mx_launch_fmt<MX_EPI_MASK_MUL, false>(g, a_fmt, b_fmt);
+  } else {
+    if (out_fp32) mx_launch_fmt<MX_EPI_NONE, true>(g, a_fmt, b_fmt);
+    else          mx_launch_fmt<MX_EPI_NONE, false>(g, a_fmt, b_fmt);
+  }
   return C;
 }

@@ -221,10 +221,11 @@ def test_mlp_fp8_fused_head_predict_matches():
     assert ((p_f8 - p_bf).abs().mean() / y.abs().mean()).item() < 0.01
 
 
-def test_mx8_supertile_clamp_path():
-    """Supertile blockIdx remap with gridDim.y not divisible by the
-    supertile height (M=768 -> 3 y-blocks, super=16 -> clamped band):
-    results must stay exact — a wrong remap drops or doubles tiles."""
+def test_mx8_three_row_blocks_exact():
+    """A grid whose row-block count is no power of two (M=768 -> 3
+    y-blocks, 2 x-blocks), through the plain GEMM and the fused head:
+    results must stay exact — a wrong block-to-tile mapping drops or
+    doubles tiles.  The suite's only MX case with three row blocks."""
     a = _randint(768, 512, 41)
     b = _randint(512, 512, 42)
     got = ops.gemm_mx8_nt(ops.quantize_e4m3(a, 0), 0,
