@@ -68,10 +68,38 @@ class GPULinearRegressor:
         self._sync_ab()
         return self
 
+    def fit_split(self, X: torch.Tensor, y: torch.Tensor,
+                  test_frac: float = 0.2, seed: int = 42,
+                  process_group=None) -> dict:
+        """Fit on the train partition of ``ops.random_split(X, y,
+        test_frac, seed)`` and return the offline metrics on its test
+        partition, without materialising either: two fused passes over
+        (X, y) with the split flag evaluated in-kernel, and two host
+        syncs (the statistics, then the metric sums).  The DP all-reduce
+        of the five statistics is the same as in :meth:`fit`."""
+        stats = ops.linreg_split_stats(X, y, test_frac, seed)
+        if process_group is not None:
+            import torch.distributed as dist
+
+            dist.all_reduce(stats, group=process_group)
+        self.intercept_, self.coef_ = ops.solve_ols(stats.cpu())
+        if X.device.type == "cuda" and self.device.type == "cuda":
+            self._ab_tensor()
+            self._sync_ab()  # the fp32 pair the scoring kernel reads
+            ab = self._ab
+        else:
+            ab = (self.intercept_, self.coef_)
+        return ops.linear_split_metrics(X, y, ab, test_frac, seed)
+
     # -- inference ---------------------------------------------------------
-    def predict(self, X: torch.Tensor) -> torch.Tensor:
+    # BatchedScorer passes a device-resident live row count to models
+    # that advertise this (the captured replay then skips pad rows)
+    SUPPORTS_LIVE_ROWS = True
+
+    def predict(self, X: torch.Tensor,
+                n_dev: torch.Tensor | None = None) -> torch.Tensor:
         if X.device.type == "cuda":
-            return ops.linear_score(X, ab=self._ab_tensor())
+            return ops.linear_score(X, ab=self._ab_tensor(), n_dev=n_dev)
         return ops.linear_score(X, self.intercept_, self.coef_)
 
     def to(self, device):

@@ -132,6 +132,22 @@ def linreg_stats(X: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     return reference.linreg_stats_cpu(X, y)
 
 
+def linreg_split_stats(
+    X: torch.Tensor, y: torch.Tensor, test_frac: float = 0.2, seed: int = 42
+) -> torch.Tensor:
+    """:func:`linreg_stats` over the TRAIN rows of
+    ``random_split(X, y, test_frac, seed)`` without materialising the
+    split: the philox flag is evaluated in the reduction kernel.  Element
+    0 of the result is the train-row count."""
+    if X.device.type == "cuda":
+        core = _core(X.device)
+        return core.linreg_split_stats(X.contiguous().float(),
+                                       y.contiguous().float(),
+                                       test_frac, seed)
+    X_tr, y_tr, _, _ = reference.random_split_cpu(X, y, test_frac, seed)
+    return reference.linreg_stats_cpu(X_tr, y_tr)
+
+
 def solve_ols(stats: torch.Tensor) -> tuple[float, float]:
     """Closed-form (intercept, coef) from fused stats (2x2 normal equations)."""
     n, sx, sy, sxx, sxy = stats.tolist()
@@ -217,19 +233,25 @@ def linear_score(
     intercept: float | None = None,
     coef: float | None = None,
     ab: torch.Tensor | None = None,
+    n_dev: torch.Tensor | None = None,
 ) -> torch.Tensor:
     """Batched linear scoring ``yhat = intercept + coef * X`` (fp32).
 
     On GPU, coefficients live in a 2-element device tensor ``ab`` read by
     the kernel, so captured serving graphs track redeployed weights
     without recapture; pass either ``ab`` or the python floats.
+
+    ``n_dev`` (int64[1] tensor on X's device) is a live row count read by
+    the kernel: only the first ``n_dev`` rows are scored and the rest of
+    the result is unspecified — a captured replay over a padded buffer
+    then costs what the live rows cost.
     """
     if X.device.type == "cuda":
         core = _core(X.device)
         if ab is None:
             ab = torch.tensor([intercept, coef], device=X.device,
                               dtype=torch.float32)
-        return core.linear_score(X.contiguous(), ab)
+        return core.linear_score(X.contiguous(), ab, n_dev)
     if ab is not None:
         intercept, coef = float(ab[0]), float(ab[1])
     return reference.linear_score_cpu(X, intercept, coef)
@@ -239,6 +261,51 @@ def linear_score(
 # metrics — reference stage_1:79-90 and stage_4:101-113
 # --------------------------------------------------------------------------
 
+def regression_metric_sums(y: torch.Tensor, yhat: torch.Tensor) -> torch.Tensor:
+    """The fused pass behind :func:`regression_metrics`: float64
+    ``[n, sum_ape, ss_res, sum_y, sum_yy, max_resid]`` on ``y``'s device."""
+    if y.device.type == "cuda":
+        core = _core(y.device)
+        return core.regression_metrics(y.contiguous(), yhat.contiguous())
+    return torch.tensor(reference.metric_sums_cpu(y, yhat),
+                        dtype=torch.float64)
+
+
+def linear_split_metric_sums(
+    X: torch.Tensor,
+    y: torch.Tensor,
+    ab,
+    test_frac: float = 0.2,
+    seed: int = 42,
+) -> torch.Tensor:
+    """:func:`regression_metric_sums` of the linear model ``ab =
+    [intercept, coef]`` (a float32[2] tensor or a pair of floats) over
+    the TEST rows of ``random_split(X, y, test_frac, seed)`` — split,
+    predict and metric reduction as one pass; element 0 is the test-row
+    count."""
+    if X.device.type == "cuda":
+        core = _core(X.device)
+        if not torch.is_tensor(ab):
+            ab = torch.tensor([float(ab[0]), float(ab[1])])
+        return core.linear_split_metrics(
+            X.contiguous().float(), y.contiguous().float(),
+            ab.to(X.device, torch.float32), test_frac, seed)
+    _, _, X_te, y_te = reference.random_split_cpu(X, y, test_frac, seed)
+    yhat = reference.linear_score_cpu(X_te, float(ab[0]), float(ab[1]))
+    return torch.tensor(reference.metric_sums_cpu(y_te, yhat),
+                        dtype=torch.float64)
+
+
+def metrics_from_sums(sums) -> dict:
+    """MAPE / R^2 / max residual from ``regression_metric_sums`` output."""
+    n, s_ape, ss_res, s_y, s_yy, max_res = (
+        sums.tolist() if torch.is_tensor(sums) else sums)
+    mape = s_ape / n
+    ss_tot = s_yy - s_y * s_y / n
+    r2 = 1.0 - ss_res / ss_tot if ss_tot > 0 else 0.0
+    return {"MAPE": mape, "r_squared": r2, "max_residual": max_res}
+
+
 def regression_metrics(y: torch.Tensor, yhat: torch.Tensor) -> dict:
     """Offline model metrics in one fused pass: MAPE, R^2, max residual.
 
@@ -247,15 +314,21 @@ def regression_metrics(y: torch.Tensor, yhat: torch.Tensor) -> dict:
     stage_1:79-90): MAPE uses |y - yhat| / max(|y|, eps).
     """
     if y.device.type == "cuda":
-        core = _core(y.device)
-        out = core.regression_metrics(y.contiguous(), yhat.contiguous())
-        n, s_ape, ss_res, s_y, s_yy, max_res = out.tolist()
-    else:
-        n, s_ape, ss_res, s_y, s_yy, max_res = reference.metric_sums_cpu(y, yhat)
-    mape = s_ape / n
-    ss_tot = s_yy - s_y * s_y / n
-    r2 = 1.0 - ss_res / ss_tot if ss_tot > 0 else 0.0
-    return {"MAPE": mape, "r_squared": r2, "max_residual": max_res}
+        return metrics_from_sums(regression_metric_sums(y, yhat))
+    return metrics_from_sums(reference.metric_sums_cpu(y, yhat))
+
+
+def linear_split_metrics(
+    X: torch.Tensor,
+    y: torch.Tensor,
+    ab,
+    test_frac: float = 0.2,
+    seed: int = 42,
+) -> dict:
+    """:func:`regression_metrics` of a linear model on the test partition
+    of the philox split, without materialising split or predictions."""
+    return metrics_from_sums(
+        linear_split_metric_sums(X, y, ab, test_frac, seed))
 
 
 def score_label_metrics(scores: torch.Tensor, labels: torch.Tensor) -> dict:

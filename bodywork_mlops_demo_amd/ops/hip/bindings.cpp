@@ -13,12 +13,18 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> random_split_hip(
     const at::Tensor& X, const at::Tensor& y, double test_frac, int64_t seed);
 // linreg.hip
 at::Tensor linreg_stats_hip(const at::Tensor& x, const at::Tensor& y);
-at::Tensor linear_score_hip(const at::Tensor& x, const at::Tensor& ab);
+at::Tensor linreg_split_stats_hip(const at::Tensor& x, const at::Tensor& y,
+                                  double test_frac, int64_t seed);
+at::Tensor linear_score_hip(const at::Tensor& x, const at::Tensor& ab,
+                            const c10::optional<at::Tensor>& n_dev);
 at::Tensor poly_stats_hip(const at::Tensor& x, const at::Tensor& y,
                           int64_t nf, double mu, double s);
 at::Tensor poly_score_hip(const at::Tensor& x, const at::Tensor& coef,
                           double mu, double s);
 at::Tensor regression_metrics_hip(const at::Tensor& y, const at::Tensor& yhat);
+at::Tensor linear_split_metrics_hip(const at::Tensor& x, const at::Tensor& y,
+                                    const at::Tensor& ab, double test_frac,
+                                    int64_t seed);
 at::Tensor score_label_metrics_hip(const at::Tensor& s, const at::Tensor& l);
 // mlp_small.hip
 std::tuple<at::Tensor, at::Tensor> expand1d_bf16_hip(
@@ -91,7 +97,11 @@ TORCH_LIBRARY(bodywork_hip, m) {
   m.def("random_split(Tensor X, Tensor y, float test_frac, int seed) -> "
         "(Tensor, Tensor, Tensor, Tensor)");
   m.def("linreg_stats(Tensor x, Tensor y) -> Tensor");
-  m.def("linear_score(Tensor x, Tensor ab) -> Tensor");
+  m.def("linreg_split_stats(Tensor x, Tensor y, float test_frac, int seed) "
+        "-> Tensor");
+  m.def("linear_score(Tensor x, Tensor ab, Tensor? n_dev) -> Tensor");
+  m.def("linear_split_metrics(Tensor x, Tensor y, Tensor ab, "
+        "float test_frac, int seed) -> Tensor");
   m.def("poly_stats(Tensor x, Tensor y, int nf, float mu, float s) -> Tensor");
   m.def("poly_score(Tensor x, Tensor coef, float mu, float s) -> Tensor");
   m.def("regression_metrics(Tensor y, Tensor yhat) -> Tensor");
@@ -139,7 +149,9 @@ TORCH_LIBRARY_IMPL(bodywork_hip, CUDA, m) {
   m.impl("datagen", datagen_hip);
   m.impl("random_split", random_split_hip);
   m.impl("linreg_stats", linreg_stats_hip);
+  m.impl("linreg_split_stats", linreg_split_stats_hip);
   m.impl("linear_score", linear_score_hip);
+  m.impl("linear_split_metrics", linear_split_metrics_hip);
   m.impl("poly_stats", poly_stats_hip);
   m.impl("poly_score", poly_score_hip);
   m.impl("regression_metrics", regression_metrics_hip);

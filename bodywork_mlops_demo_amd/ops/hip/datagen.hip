@@ -168,7 +168,9 @@ std::tuple<at::Tensor, at::Tensor> datagen_hip(
   auto counts = at::empty({n_blocks}, u32);
   auto offsets = at::empty({n_blocks}, u32);
   auto chunk_sums = at::empty({std::max<long long>(n_chunks, 1)}, u32);
-  auto total = at::zeros({1}, u32);
+  // scan_level2 always writes the total; int32 storage (count <= n < 2^31)
+  // so the host can read it back without a dtype-conversion kernel
+  auto total = at::empty({1}, opts.dtype(at::kInt));
 
   unsigned int key0 = (unsigned int)(seed & 0xFFFFFFFFll);
   unsigned int key1 = (seed > 0xFFFFFFFFll) ? (unsigned int)(seed >> 32)
@@ -200,7 +202,7 @@ std::tuple<at::Tensor, at::Tensor> datagen_hip(
                      y_out.data_ptr<float>(), X_out.data_ptr<float>(),
                      (long long)n);
   // one D2H sync to size the result (datagen is per-cycle, not per-request)
-  int64_t kept = total.to(at::kLong).item<int64_t>();
+  int64_t kept = total.item<int32_t>();
   return {y_out.narrow(0, 0, kept), X_out.narrow(0, 0, kept)};
 }
 
@@ -283,6 +285,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> random_split_hip(
   TORCH_CHECK(X.is_cuda() && y.is_cuda() && X.numel() == y.numel());
   TORCH_CHECK(X.scalar_type() == at::kFloat && y.scalar_type() == at::kFloat);
   long long n = X.numel();
+  if (n == 0) return {X, y, X, y};
   const long long n_blocks = (n + DG_BLOCK - 1) / DG_BLOCK;
   const long long n_chunks = (n_blocks + SCAN_CHUNK - 1) / SCAN_CHUNK;
   TORCH_CHECK(n_chunks <= 4096, "random_split: n too large (max ~1.07e9)");
@@ -290,7 +293,8 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> random_split_hip(
   auto counts = at::empty({n_blocks}, u32);
   auto offsets = at::empty({n_blocks}, u32);
   auto chunk_sums = at::empty({std::max<long long>(n_chunks, 1)}, u32);
-  auto total = at::zeros({1}, u32);
+  // written by scan_level2; int32 (count <= n < 2^31) reads back directly
+  auto total = at::empty({1}, X.options().dtype(at::kInt));
   unsigned int key0 = (unsigned int)(seed & 0xFFFFFFFFll);
   unsigned int key1 = (seed > 0xFFFFFFFFll) ? (unsigned int)(seed >> 32)
                                             : 0x85EBCA6Bu;  // split stream
@@ -320,7 +324,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> random_split_hip(
                      X_tr.data_ptr<float>(), y_tr.data_ptr<float>(),
                      X_te.data_ptr<float>(), y_te.data_ptr<float>(), n, key0,
                      key1, tau);
-  int64_t n_test = total.to(at::kLong).item<int64_t>();
+  int64_t n_test = total.item<int32_t>();
   int64_t n_train = n - n_test;
   return {X_tr.narrow(0, 0, n_train), y_tr.narrow(0, 0, n_train),
           X_te.narrow(0, 0, n_test), y_te.narrow(0, 0, n_test)};

@@ -21,14 +21,8 @@ __device__ __forceinline__ double wave_max_f64(double v) {
   return v;
 }
 
-// atomic max for NON-NEGATIVE doubles: the IEEE bit pattern of x>=0 is
-// monotonic as an unsigned integer, so u64 atomicMax is a double max.
-__device__ __forceinline__ void atomic_max_nonneg_f64(double* addr, double v) {
-  atomicMax((unsigned long long*)addr, __double_as_longlong(v));
-}
-
-// block-level sum: per-wave shuffle reduce -> LDS -> wave-0 combine,
-// then ONE atomicAdd per block (Guideline 12).
+// block-level sum: per-wave shuffle reduce -> LDS -> wave-0 combine.
+// The combine order is fixed, so the result is bitwise reproducible.
 // NWAVES = blockDim.x / 64 (<= 16).
 template <int NWAVES>
 __device__ __forceinline__ double block_sum_f64(double v, double* lds_scratch) {
@@ -45,4 +39,21 @@ __device__ __forceinline__ double block_sum_f64(double v, double* lds_scratch) {
   }
   __syncthreads();  // scratch reusable by the caller afterwards
   return total;  // valid in wave 0 (all lanes)
+}
+
+// block-level max, same shape as block_sum_f64 (valid in wave 0).
+template <int NWAVES>
+__device__ __forceinline__ double block_max_f64(double v, double* lds_scratch) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  v = wave_max_f64(v);
+  if (lane == 0) lds_scratch[wave] = v;
+  __syncthreads();
+  double total = 0.0;
+  if (wave == 0) {
+    total = lds_scratch[lane < NWAVES ? lane : 0];
+    total = wave_max_f64(total);
+  }
+  __syncthreads();
+  return total;
 }

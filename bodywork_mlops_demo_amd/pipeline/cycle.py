@@ -136,16 +136,24 @@ class CycleState:
         return self.cycle_count % max(self.world_size, 1)
 
     # -- async artefact I/O: dataset D2H copies run on a side stream
-    #    through double-buffered pinned staging and the file write runs
-    #    on the I/O thread after the copy event fires, overlapping the
-    #    next stages' compute.  drain_io() before reading artefacts back
-    #    or stopping a benchmark clock.
-    def submit_io(self, fn, *args) -> None:
+    #    through a ring of pinned staging pairs and the file writes run
+    #    on I/O threads after the copy event fires, overlapping the
+    #    next stages' compute.  Consecutive days are separate files, so
+    #    two writes are in flight at once (a single writer copying into
+    #    the page cache was the longest serial chain of a 10M-row cycle).
+    #    drain_io() before reading artefacts back or stopping a
+    #    benchmark clock.
+    IO_WORKERS = 2
+    PIN_SLOTS = 3  # one being filled + one per writer
+
+    def submit_io(self, fn, *args):
         if self._io_pool is None:
             from concurrent.futures import ThreadPoolExecutor
 
-            self._io_pool = ThreadPoolExecutor(max_workers=1)
-        self._io_futures.append(self._io_pool.submit(fn, *args))
+            self._io_pool = ThreadPoolExecutor(max_workers=self.IO_WORKERS)
+        fut = self._io_pool.submit(fn, *args)
+        self._io_futures.append(fut)
+        return fut
 
     def drain_io(self) -> None:
         for f in self._io_futures:
@@ -166,24 +174,25 @@ class CycleState:
         """Persist a day's dataset without blocking the pipeline: the D2H
         copies run on a side stream through cached pinned buffers
         (overlapping the next stage's compute) and the file write runs on
-        the I/O thread after the copy event fires.  Pinned buffers are
-        reused only after drain_io()."""
+        an I/O thread after the copy event fires.  A pinned pair is
+        reused only after the write that last used it has finished."""
         if y.device.type != "cuda":
             self.submit_io(store.put_dataset, d, y.numpy(), X.numpy(), fmt)
             return
-        # double-buffered pinned staging: only the write that used THIS
-        # buffer pair (two cycles ago) must be awaited — with the serial
-        # I/O worker that future is normally long done, so the pipeline
-        # never stalls on its own artefact I/O
-        flip = getattr(self, "_pin_flip", 0) ^ 1
-        self._pin_flip = flip
+        # ring of pinned staging pairs, each guarded by the future of the
+        # write that last used it (PIN_SLOTS persists ago): with two
+        # writers that future is normally done, so the pipeline does not
+        # stall on its own artefact I/O
+        slot = getattr(self, "_pin_slot", -1) + 1
+        slot %= self.PIN_SLOTS
+        self._pin_slot = slot
         if getattr(self, "_pin_futures", None) is None:
             self._pin_futures = {}
-        prev = self._pin_futures.get(flip)
+        prev = self._pin_futures.get(slot)
         if prev is not None:
             prev.result()
-        yv = self._pin_view(f"y{flip}", y.numel(), y.dtype)
-        Xv = self._pin_view(f"X{flip}", X.numel(), X.dtype)
+        yv = self._pin_view(f"y{slot}", y.numel(), y.dtype)
+        Xv = self._pin_view(f"X{slot}", X.numel(), X.dtype)
         if getattr(self, "_io_stream", None) is None:
             self._io_stream = torch.cuda.Stream()
         ev = torch.cuda.Event()
@@ -202,12 +211,28 @@ class CycleState:
             ev.synchronize()
             store.put_dataset(d, yv.numpy(), Xv.numpy(), fmt)
 
-        fut_idx = len(self._io_futures)
-        self.submit_io(_write)
-        self._pin_futures[flip] = self._io_futures[fut_idx]
+        self._pin_futures[slot] = self.submit_io(_write)
 
     def append_day(self, y: torch.Tensor, X: torch.Tensor) -> None:
         add = int(y.shape[0])
+        self._day_sizes.append(add)
+        if self.history_days is not None:
+            # drop expired days BEFORE appending: a window that keeps
+            # nothing old (history_days=1) then costs just the two
+            # copies of the new day
+            drop = 0
+            while len(self._day_sizes) > max(self.history_days, 1):
+                drop += self._day_sizes.pop(0)
+            if drop:
+                keep = self._n - drop
+                if keep > 0:
+                    src_y = self._buf_y[drop:self._n]
+                    src_X = self._buf_X[drop:self._n]
+                    if keep > drop:  # source and destination overlap
+                        src_y, src_X = src_y.clone(), src_X.clone()
+                    self._buf_y[:keep].copy_(src_y)
+                    self._buf_X[:keep].copy_(src_X)
+                self._n = keep
         need = self._n + add
         if need > self._buf_y.numel():
             cap = max(need, 2 * self._buf_y.numel())
@@ -220,18 +245,6 @@ class CycleState:
         self._buf_y[self._n:need].copy_(y)
         self._buf_X[self._n:need].copy_(X)
         self._n = need
-        self._day_sizes.append(add)
-        if self.history_days is not None:
-            drop = 0
-            while len(self._day_sizes) > self.history_days:
-                drop += self._day_sizes.pop(0)
-            if drop:
-                keep = self._n - drop
-                # overlapping region: stage through a clone (fixed-size
-                # transient the allocator reuses)
-                self._buf_y[:keep].copy_(self._buf_y[drop:self._n].clone())
-                self._buf_X[:keep].copy_(self._buf_X[drop:self._n].clone())
-                self._n = keep
 
 
 def run_cycle(
@@ -280,8 +293,11 @@ def run_cycle(
         skip_train = False  # nothing deployed yet -> must train
 
     def sync():
+        # the compute stream only: a device-wide sync would also wait for
+        # the dataset D2H on the I/O stream and put it back on the
+        # critical path
         if dev_cuda:
-            torch.cuda.synchronize()
+            torch.cuda.current_stream(torch.device(device)).synchronize()
 
     # -- day-0 bootstrap: make sure there is data for today -----------------
     if state.y.numel() == 0:

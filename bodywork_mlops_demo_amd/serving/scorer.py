@@ -9,8 +9,12 @@ sizes so the per-request launch overhead disappears from the hot loop
 
 Graph strategy: power-of-two batch buckets, one captured graph per
 bucket, static input/output buffers; a request is padded up to its
-bucket, replayed, and sliced.  Capture is lazy (first use of a bucket)
-and falls back to direct launches on CPU or when capture is unavailable.
+bucket, replayed, and sliced.  Models whose kernels can read a live row
+count from device memory (``SUPPORTS_LIVE_ROWS``: the linear model) are
+not padded: the bucket keeps an int64 count tensor that is updated before
+each replay, and the captured kernel stops at that row.  Capture is lazy
+(first use of a bucket) and falls back to direct launches on CPU or when
+capture is unavailable.
 """
 from __future__ import annotations
 
@@ -38,6 +42,7 @@ class BatchedScorer:
         # elementwise models batch up to 2^24 rows per graph replay
         max_bucket = int(getattr(model, "PREDICT_CHUNK", 1 << 24))
         self.buckets = [b for b in self.BUCKETS if b <= max_bucket]
+        self._live_rows = bool(getattr(model, "SUPPORTS_LIVE_ROWS", False))
 
     def _bucket(self, n: int) -> int:
         for b in self.buckets:
@@ -57,13 +62,20 @@ class BatchedScorer:
 
     def _capture(self, b: int):
         x_static = torch.zeros(b, device=self.device, dtype=torch.float32)
+        n_static = None
+        predict = self.model.predict
+        if self._live_rows:
+            n_static = torch.zeros(1, device=self.device, dtype=torch.int64)
+
+            def predict(x, _n=n_static):
+                return self.model.predict(x, n_dev=_n)
         # warm up kernel/launch state on a side stream before capture —
         # a SMALL batch suffices (warmup exists for lazy init, not shape)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(2):
-                self.model.predict(x_static[: min(b, 1024)])
+                predict(x_static[: min(b, 1024)])
         torch.cuda.current_stream().wait_stream(s)
         # thread_local capture mode: the serving process has background
         # threads (uvicorn workers, torch allocator/event threads) whose
@@ -77,13 +89,13 @@ class BatchedScorer:
             try:
                 with torch.cuda.graph(graph,
                                       capture_error_mode="thread_local"):
-                    y_static = self.model.predict(x_static)
+                    y_static = predict(x_static)
                 break
             except RuntimeError:
                 if attempt == 1:
                     raise
                 torch.cuda.synchronize()
-        self._graphs[b] = (graph, x_static, y_static)
+        self._graphs[b] = (graph, x_static, y_static, n_static)
         log.info(f"captured scoring hipGraph for batch bucket {b}")
 
     def score_tensor(self, X: torch.Tensor) -> torch.Tensor:
@@ -116,9 +128,11 @@ class BatchedScorer:
                             f"direct launch\n{traceback.format_exc()}")
                 self.use_graphs = False
                 return self.model.predict(X)
-        graph, x_static, y_static = self._graphs[b]
+        graph, x_static, y_static, n_static = self._graphs[b]
         x_static[:n] = X.to(self.device, dtype=torch.float32)
-        if n < b:
+        if n_static is not None:
+            n_static.fill_(n)  # the replayed kernel stops at row n
+        elif n < b:
             x_static[n:] = 1.0  # benign pad (avoids log/div edge cases)
         graph.replay()
         return y_static[:n].clone()

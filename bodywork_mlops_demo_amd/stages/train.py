@@ -70,14 +70,20 @@ def run(
 
     n = X.shape[0]
     log.info(f"training {model_type} regressor on {n} rows (device={device})")
-    # fused on-device philox split (reference: 80/20, seed 42 —
+    # on-device philox split (reference: 80/20, seed 42 —
     # stage_1:98-103); count is binomial(n, 0.2) rather than exactly n/5
-    X_train, y_train, X_test, y_test = ops.random_split(X, y, 0.2, seed=42)
+    metrics = None
+    if model_type != "linear":
+        X_train, y_train, X_test, y_test = ops.random_split(X, y, 0.2,
+                                                            seed=42)
 
     if model_type == "linear":
-        model = GPULinearRegressor(device=device).fit(
-            X_train, y_train, process_group=process_group
-        )
+        # the linear fit and its offline metrics are two streaming
+        # reductions, so the same split is evaluated inside them instead
+        # of being scattered into four arrays that are each read once
+        model = GPULinearRegressor(device=device)
+        metrics = model.fit_split(X, y, 0.2, seed=42,
+                                  process_group=process_group)
     elif model_type.startswith("poly"):
         # "poly" (degree 3) or "poly<d>", e.g. "poly2"
         degree = int(model_type[4:]) if len(model_type) > 4 else 3
@@ -109,8 +115,9 @@ def run(
     else:
         raise ValueError(f"unknown model_type {model_type!r}")
 
-    yhat = model.predict(X_test)
-    metrics = ops.regression_metrics(y_test, yhat)
+    if metrics is None:
+        yhat = model.predict(X_test)
+        metrics = ops.regression_metrics(y_test, yhat)
     log.info(f"offline metrics: {metrics}")
 
     if rank == 0:
