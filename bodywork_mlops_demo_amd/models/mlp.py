@@ -275,10 +275,17 @@ class GPUMLPRegressor:
         return [self.w1, self.b1, self.W2, self.b2, self.w3, self.b3]
 
     # -- forward -----------------------------------------------------------
-    def _forward(self, x: torch.Tensor, want_masks: bool = False):
+    def _forward(self, x: torch.Tensor, want_masks: bool = False,
+                 n_dev: torch.Tensor | None = None):
         """Forward pass; with ``want_masks`` the relu layers also emit
         their 1-bit activation masks (consumed by the masked backward —
-        16x less mask traffic than re-reading the activations)."""
+        16x less mask traffic than re-reading the activations).
+
+        ``n_dev`` (scoring only; see :meth:`predict`) reaches the two
+        tile-gated scoring branches, whose kernels stop at that row; every
+        other branch ignores it and computes all rows."""
+        if want_masks and n_dev is not None:
+            raise ValueError("the training forward takes no live row count")
         xn = (x.float() - self.X_MU) / self.X_SIGMA
         if want_masks and self._use_fp8_train(xn.shape[0]):
             # fp8 training forward: dual-emit layer 1 (bf16 + mask for the
@@ -304,17 +311,19 @@ class GPUMLPRegressor:
             # never touches HBM
             self._ensure_fp8_weights()
             h1q = ops.expand1d_e4m3(xn, self.w1_bf, self.b1_bf,
-                                    self._e_h1)
+                                    self._e_h1, n_dev=n_dev)
             yhat = ops.gemm_mx8_relu_dot(h1q, self._e_h1, self._w2_q8,
-                                         self._e_w2, self.b2, self.w3)
+                                         self._e_w2, self.b2, self.w3,
+                                         n_dev=n_dev)
             yhat = yhat + self.b3
             return yhat, h1q, None, xn, None, None
         elif self._use_fused_head(xn.shape[0]):
             # bf16 fused head: h2 GEMM + relu + rowdot in one kernel
             # (the fp8 path's structure at bf16 precision)
-            h1 = ops.expand1d_bf16(xn, self.w1_bf, self.b1_bf, relu=True)
+            h1 = ops.expand1d_bf16(xn, self.w1_bf, self.b1_bf, relu=True,
+                                   n_dev=n_dev)
             yhat = ops.linear_relu_dot_bf16(h1, self.W2w_bf, self.b2,
-                                            self.w3)
+                                            self.w3, n_dev=n_dev)
             yhat = yhat + self.b3
             return yhat, h1, None, xn, None, None
         else:
@@ -347,11 +356,27 @@ class GPUMLPRegressor:
     #: 2 * chunk * H bf16 (= 16 GiB at H=4096) however large the batch
     PREDICT_CHUNK = 1 << 20
 
-    def predict(self, X: torch.Tensor) -> torch.Tensor:
+    #: predict() takes a device-side live row count (BatchedScorer then
+    #: replays its padded buckets without paying for the pad rows)
+    SUPPORTS_LIVE_ROWS = True
+
+    def predict(self, X: torch.Tensor,
+                n_dev: torch.Tensor | None = None) -> torch.Tensor:
+        """Score ``X``.  ``n_dev`` (int64[1] tensor on the model's device)
+        is a live row count that the kernels read at run time: rows
+        ``< n_dev`` of the result are right, the rest unspecified.  On the
+        GPU, batches of a multiple of 256 rows skip the work past the
+        count (row tiles of the fused head return at once); other batch
+        sizes, and the CPU, ignore it and compute every row."""
         X = X.to(self.device)
         n = X.shape[0]
+        if n_dev is not None and n > self.PREDICT_CHUNK:
+            raise ValueError(
+                f"predict with a live row count serves at most "
+                f"PREDICT_CHUNK={self.PREDICT_CHUNK} rows (got {n}): one "
+                "count cannot describe several chunks")
         if n <= self.PREDICT_CHUNK:
-            return self._forward(X)[0]
+            return self._forward(X, n_dev=n_dev)[0]
         out = torch.empty(n, dtype=torch.float32, device=self.device)
         for lo in range(0, n, self.PREDICT_CHUNK):
             hi = min(lo + self.PREDICT_CHUNK, n)

@@ -490,17 +490,23 @@ def expand1d_e4m3(
     w: torch.Tensor,
     b: torch.Tensor | None,
     e: int,
+    n_dev: torch.Tensor | None = None,
 ) -> torch.Tensor:
     """h = relu(x*w + b) emitted DIRECTLY as e4m3 bytes (value = 2^e *
     stored) — the MLP fp8 scoring forward's fused layer 1.  Unfused the
     path costs 5 HBM bytes per element (bf16 write + re-read + fp8
     write); fused it costs 1.  CPU oracle: quantize_e4m3_cpu of the
-    bf16-rounded activation."""
+    bf16-rounded activation.
+
+    ``n_dev`` (int64[1] tensor on x's device) is a live row count read by
+    the kernel: only the first ``n_dev`` rows (clamped to [0, n]) are
+    written, the rest of the result is unspecified.  The CPU oracle
+    computes every row."""
     if x.device.type == "cuda":
         core = _core(x.device)
         return core.expand1d_e4m3(
             x.contiguous(), w.contiguous(),
-            b.contiguous() if b is not None else None, int(e))
+            b.contiguous() if b is not None else None, int(e), n_dev)
     h = reference.expand1d_cpu(x, w, b, relu=True).float()
     return reference.quantize_e4m3_cpu(h, int(e))
 
@@ -541,6 +547,7 @@ def gemm_mx8_relu_dot(
     eb: int,
     b2: torch.Tensor,
     w3: torch.Tensor,
+    n_dev: torch.Tensor | None = None,
 ) -> torch.Tensor:
     """y[M] = Σ_col relu(2^(ea+eb)·(a8·b8ᵀ) + b2) * w3 — the MLP scoring
     forward's hot GEMM and the rowdot head fused into ONE kernel.
@@ -550,15 +557,33 @@ def gemm_mx8_relu_dot(
     wave butterfly-reduces its 64-column strip in registers and fl==0
     lanes accumulate per-row partials with fp32 atomics.  Caller adds
     the scalar output bias.  CPU oracle: decode + matmul + relu + dot.
+
+    ``n_dev`` (int64[1] tensor on a8's device) is a live row count read
+    by the kernel and clamped to [0, M]: row tiles past it return before
+    staging anything, rows ``>= n_dev`` of y are exactly 0 and whatever
+    their a8 rows hold (NaN bytes included) reaches no live row — a
+    captured replay over a padded bucket costs what the live tiles cost.
     """
     if a8.device.type == "cuda":
         core = _core(a8.device)
         return core.gemm_mx8_relu_dot(a8.contiguous(), int(ea),
                                       b8.contiguous(), int(eb),
-                                      b2.contiguous(), w3.contiguous())
+                                      b2.contiguous(), w3.contiguous(),
+                                      n_dev)
     h2 = reference.gemm_mx8_nt_cpu(a8, ea, b8, eb, bias=b2, relu=True,
                                    out_fp32=True)
-    return h2 @ w3.float()
+    return _zero_dead_rows(h2 @ w3.float(), n_dev)
+
+
+def _zero_dead_rows(y: torch.Tensor, n_dev: torch.Tensor | None):
+    """CPU oracle of the fused heads' live row count: rows at or past
+    ``n_dev`` (clamped to [0, M]) are 0."""
+    if n_dev is None:
+        return y
+    n = min(max(int(n_dev.reshape(-1)[0]), 0), y.shape[0])
+    y = y.clone()
+    y[n:] = 0.0
+    return y
 
 
 def gemm_mx8_relu_mask(
@@ -732,18 +757,21 @@ def linear_relu_dot_bf16(
     w: torch.Tensor,
     b2: torch.Tensor,
     w3: torch.Tensor,
+    n_dev: torch.Tensor | None = None,
 ) -> torch.Tensor:
     """y[M] = Σ_col relu(x[M,K] @ w[N,K]ᵀ + b2) * w3 — the bf16 MLP
     scoring forward's hot GEMM and rowdot head fused into one kernel
     (the bf16 twin of gemm_mx8_relu_dot: the [M,N] activation never
     reaches HBM).  Requires M%256==0, N%256==0, K%128==0.
+    ``n_dev``: live row count, same contract as gemm_mx8_relu_dot's.
     CPU oracle: fp32 matmul + relu + dot."""
     if x.device.type == "cuda":
         core = _core(x.device)
         return core.gemm8_relu_dot_bf16(x.contiguous(), w.contiguous(),
-                                        b2.contiguous(), w3.contiguous())
+                                        b2.contiguous(), w3.contiguous(),
+                                        n_dev)
     h2 = torch.relu(x.float() @ w.float().t() + b2.float())
-    return h2 @ w3.float()
+    return _zero_dead_rows(h2 @ w3.float(), n_dev)
 
 
 def transpose_bf16(src: torch.Tensor) -> torch.Tensor:
@@ -761,6 +789,7 @@ def expand1d_bf16(
     relu: bool = False,
     mask: torch.Tensor | None = None,
     emit_mask: bool = False,
+    n_dev: torch.Tensor | None = None,
 ):
     """Fused rank-1 expansion: out[i,j] = act(x[i]*w[j] + b[j]).
 
@@ -771,7 +800,17 @@ def expand1d_bf16(
     activations; ``emit_mask`` additionally returns that bitmask for the
     produced activations.  Returns bf16 (n, H) (or a (out, maskbits)
     pair when ``emit_mask``).
+
+    ``n_dev`` (int64[1] tensor on x's device; plain ``relu=True`` scoring
+    use only, no ``mask``/``emit_mask``) is a live row count read by the
+    kernel: only the first ``n_dev`` rows (clamped to [0, n]) are written,
+    the rest of the result is unspecified.  The CPU oracle computes every
+    row.
     """
+    if n_dev is not None and (mask is not None or emit_mask or not relu):
+        raise ValueError(
+            "expand1d_bf16: n_dev serves the plain relu scoring use only "
+            "(relu=True, no mask, no emit_mask)")
     if x.device.type == "cuda":
         core = _core(x.device)
         out, mbits = core.expand1d_bf16(
@@ -780,6 +819,7 @@ def expand1d_bf16(
             relu,
             mask.contiguous() if mask is not None else None,
             emit_mask,
+            n_dev,
         )
         return (out, mbits) if emit_mask else out
     return reference.expand1d_cpu(x, w, b, relu, mask, emit_mask)

@@ -30,7 +30,8 @@ at::Tensor score_label_metrics_hip(const at::Tensor& s, const at::Tensor& l);
 std::tuple<at::Tensor, at::Tensor> expand1d_bf16_hip(
     const at::Tensor& x, const at::Tensor& w,
     const c10::optional<at::Tensor>& b, bool relu,
-    const c10::optional<at::Tensor>& mask, bool emit_mask);
+    const c10::optional<at::Tensor>& mask, bool emit_mask,
+    const c10::optional<at::Tensor>& n_dev);
 at::Tensor rowdot_bf16_hip(const at::Tensor& h, const at::Tensor& w,
                            const at::Tensor& bias);
 at::Tensor coldot_bf16_hip(const at::Tensor& m, const at::Tensor& v,
@@ -48,19 +49,21 @@ at::Tensor gemm_tn_bf16_hip(const at::Tensor& a, const at::Tensor& b,
                             bool out_fp32);
 // gemm8.hip
 at::Tensor gemm8_relu_dot_bf16_hip(const at::Tensor& x, const at::Tensor& w,
-                                   const at::Tensor& b2,
-                                   const at::Tensor& w3);
+                                   const at::Tensor& b2, const at::Tensor& w3,
+                                   const c10::optional<at::Tensor>& n_dev);
 // gemm_mx8.hip — MX-fp8 (e4m3 / e5m2) K=128 scaled-MFMA path
 at::Tensor quantize_e4m3_hip(const at::Tensor& x, int64_t e);
 at::Tensor expand1d_e4m3_hip(const at::Tensor& x, const at::Tensor& w,
-                             const c10::optional<at::Tensor>& b, int64_t e);
+                             const c10::optional<at::Tensor>& b, int64_t e,
+                             const c10::optional<at::Tensor>& n_dev);
 at::Tensor gemm_mx8_nt_hip(const at::Tensor& a8, int64_t ea,
                            const at::Tensor& b8, int64_t eb,
                            const c10::optional<at::Tensor>& bias, bool relu,
                            bool out_fp32);
 at::Tensor gemm_mx8_relu_dot_hip(const at::Tensor& a8, int64_t ea,
                                  const at::Tensor& b8, int64_t eb,
-                                 const at::Tensor& b2, const at::Tensor& w3);
+                                 const at::Tensor& b2, const at::Tensor& w3,
+                                 const c10::optional<at::Tensor>& n_dev);
 std::tuple<at::Tensor, at::Tensor, at::Tensor> expand1d_bf16_e4m3_hip(
     const at::Tensor& x, const at::Tensor& w,
     const c10::optional<at::Tensor>& b, int64_t e);
@@ -107,7 +110,7 @@ TORCH_LIBRARY(bodywork_hip, m) {
   m.def("regression_metrics(Tensor y, Tensor yhat) -> Tensor");
   m.def("score_label_metrics(Tensor s, Tensor l) -> Tensor");
   m.def("expand1d_bf16(Tensor x, Tensor w, Tensor? b, bool relu, "
-        "Tensor? mask, bool emit_mask) -> (Tensor, Tensor)");
+        "Tensor? mask, bool emit_mask, Tensor? n_dev) -> (Tensor, Tensor)");
   m.def("rowdot_bf16(Tensor h, Tensor w, Tensor bias) -> Tensor");
   m.def("coldot_bf16(Tensor m, Tensor v, bool also_colsum) -> Tensor");
   m.def("colsum_bf16(Tensor m) -> Tensor");
@@ -117,11 +120,12 @@ TORCH_LIBRARY(bodywork_hip, m) {
         "(Tensor, Tensor)");
   m.def("gemm_tn_bf16(Tensor a, Tensor b, bool out_fp32) -> Tensor");
   m.def("quantize_e4m3(Tensor x, int e) -> Tensor");
-  m.def("expand1d_e4m3(Tensor x, Tensor w, Tensor? b, int e) -> Tensor");
+  m.def("expand1d_e4m3(Tensor x, Tensor w, Tensor? b, int e, Tensor? n_dev) "
+        "-> Tensor");
   m.def("gemm_mx8_nt(Tensor a8, int ea, Tensor b8, int eb, Tensor? bias, "
         "bool relu, bool out_fp32) -> Tensor");
   m.def("gemm_mx8_relu_dot(Tensor a8, int ea, Tensor b8, int eb, "
-        "Tensor b2, Tensor w3) -> Tensor");
+        "Tensor b2, Tensor w3, Tensor? n_dev) -> Tensor");
   m.def("expand1d_bf16_e4m3(Tensor x, Tensor w, Tensor? b, int e) -> "
         "(Tensor, Tensor, Tensor)");
   m.def("gemm_mx8_relu_mask(Tensor a8, int ea, Tensor b8, int eb, "
@@ -134,8 +138,8 @@ TORCH_LIBRARY(bodywork_hip, m) {
   m.def("gemm_mx8_nt_fmt(Tensor a8, int ea, Tensor? ea_dev, Tensor b8, "
         "int eb, Tensor? eb_dev, int a_fmt, int b_fmt, Tensor? mask, "
         "bool out_fp32) -> Tensor");
-  m.def("gemm8_relu_dot_bf16(Tensor x, Tensor w, Tensor b2, Tensor w3) "
-        "-> Tensor");
+  m.def("gemm8_relu_dot_bf16(Tensor x, Tensor w, Tensor b2, Tensor w3, "
+        "Tensor? n_dev) -> Tensor");
   m.def("adam_step(Tensor(a!) p, Tensor g, Tensor(b!) m, Tensor(c!) v, "
         "Tensor(d!)? p_bf16, float lr, float beta1, float beta2, float eps, "
         "int t, Tensor? bc) -> ()");

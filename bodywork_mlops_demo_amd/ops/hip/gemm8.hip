@@ -65,6 +65,9 @@ typedef __attribute__((ext_vector_type(4))) float g8_f32x4;
 // (the [M,N] activation never reaches HBM — mirrors gemm_mx8.hip's
 // MX_EPI_RELU_DOT).  In this mode the `mask` kernel argument carries
 // w3 (const float*) and C is y (fp32 [M], caller-zeroed).
+// LIVE (this epilogue only): the kernel reads a live row count from device
+// memory; row tiles past it return at once and rows at or past it add
+// nothing to y (same contract as gemm_mx8.hip's head).
 #define G8_EPI_RELU_DOT 3
 
 __device__ __forceinline__ void g8_glds16(const void* gsrc, void* lds_dst) {
@@ -87,12 +90,14 @@ __device__ __forceinline__ void g8_stage_half(short* __restrict__ slot,
   g8_glds16(base + off0, (char*)slot + wave * 1024);
 }
 
-template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK>
+template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK,
+          bool LIVE = false>
 __device__ __forceinline__ void g8_epilogue(
     g8_f32x4 (&acc)[4][4], const float* __restrict__ bias,
     const unsigned char* __restrict__ mask,
     unsigned char* __restrict__ mask_out, void* __restrict__ C, long long M,
-    long long N, long long m0, long long n0, int wm, int wn, int fl, int kg) {
+    long long N, long long m0, long long n0, int wm, int wn, int fl, int kg,
+    int live_rows = G8_BM) {  // LIVE: this tile's rows below the live count
   if (EPI == G8_EPI_RELU_DOT) {
     const float* w3 = (const float*)mask;
     float w3v[4], b2v[4];
@@ -113,7 +118,9 @@ __device__ __forceinline__ void g8_epilogue(
 #pragma unroll
         for (int m = 1; m < 16; m <<= 1)
           part += __shfl_xor(part, m, 64);  // reduce across fl (lane&15)
-        if (fl == 0) {
+        // LIVE: a 32-bit compare of the row's place in the tile
+        if (fl == 0 &&
+            (!LIVE || wm * 64 + i * 16 + kg * 4 + r < live_rows)) {
           long long row = m0 + wm * 64 + i * 16 + kg * 4 + r;
           atomicAdd((float*)C + row, part);
         }
@@ -181,17 +188,32 @@ __device__ __forceinline__ void g8_epilogue(
   }
 }
 
-template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false>
+template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false,
+          bool LIVE = false>
 __launch_bounds__(G8_THREADS)
 __global__ void gemm_nt_8phase_kernel(
     const bf16_t* __restrict__ A,  // [M,K]
     const bf16_t* __restrict__ B,  // [N,K]
     const float* __restrict__ bias, const unsigned char* __restrict__ mask,
     unsigned char* __restrict__ mask_out, void* __restrict__ C, long long M,
-    long long N, long long K) {
+    long long N, long long K,
+    const int64_t* __restrict__ n_live = nullptr) {  // LIVE only
   // ONE __shared__ object (guide §5 trap (a))
   __shared__ short lds[8 * G8_HT];  // [op A=0/B=1][buf][half][128][64]
   const long long m0 = (long long)blockIdx.y * G8_BM;
+  // LIVE: a captured scoring graph keeps its bucket-sized grid and reads
+  // the request's row count (device int64[1], clamped to [0, M]) here.  A
+  // row tile past it returns before the first glds, barrier or LDS access;
+  // the test is block-uniform and the count stays in SGPRs (the kernel has
+  // no VGPR to spare).
+  int live_rows = G8_BM;
+  if constexpr (LIVE) {
+    static_assert(EPI == G8_EPI_RELU_DOT, "live rows: scoring head only");
+    long long live = (long long)*n_live;
+    live = live < 0 ? 0 : (live < M ? live : M);
+    if (m0 >= live) return;
+    live_rows = (int)(live - m0 < G8_BM ? live - m0 : G8_BM);
+  }
   const long long n0 = (long long)blockIdx.x * G8_BN;
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
@@ -355,16 +377,18 @@ __global__ void gemm_nt_8phase_kernel(
 #undef G8_ASLOT
 #undef G8_BSLOT
 
-  g8_epilogue<EPI, HAS_BIAS, OUT_FP32, EMIT_MASK>(
-      acc, bias, mask, mask_out, C, M, N, m0, n0, wm, wn, fl, kg);
+  g8_epilogue<EPI, HAS_BIAS, OUT_FP32, EMIT_MASK, LIVE>(
+      acc, bias, mask, mask_out, C, M, N, m0, n0, wm, wn, fl, kg, live_rows);
 }
 
 // y[M] = sum_col relu(x.w^T + b2) * w3 — the bf16 MLP scoring forward's
 // h2 GEMM and rowdot head in ONE kernel (the [M,N] activation tensor
-// never reaches HBM).  Caller adds b3.
+// never reaches HBM).  Caller adds b3.  With n_dev (int64[1] on x's
+// device) the row tiles past that live count return at once and
+// y[n_dev:] stays 0.
 at::Tensor gemm8_relu_dot_bf16_hip(const at::Tensor& x, const at::Tensor& w,
-                                   const at::Tensor& b2,
-                                   const at::Tensor& w3) {
+                                   const at::Tensor& b2, const at::Tensor& w3,
+                                   const c10::optional<at::Tensor>& n_dev) {
   TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.dim() == 2 && w.dim() == 2 &&
                   x.size(1) == w.size(1),
               "gemm8_relu_dot: [M,K]x[N,K] cuda");
@@ -378,15 +402,27 @@ at::Tensor gemm8_relu_dot_bf16_hip(const at::Tensor& x, const at::Tensor& w,
                   b2.numel() == N, "b2: fp32 [N]");
   TORCH_CHECK(w3.is_cuda() && w3.scalar_type() == at::kFloat &&
                   w3.numel() == N, "w3: fp32 [N]");
+  const int64_t* n_live = nullptr;
+  if (n_dev.has_value() && n_dev->defined()) {
+    TORCH_CHECK(n_dev->is_cuda() && n_dev->device() == x.device() &&
+                    n_dev->numel() == 1 && n_dev->scalar_type() == at::kLong,
+                "gemm8_relu_dot: n_dev must be an int64[1] tensor on x's "
+                "device");
+    n_live = n_dev->data_ptr<int64_t>();
+  }
   auto y = at::zeros({M}, x.options().dtype(at::kFloat));
   dim3 grid((unsigned)(N / G8_BN), (unsigned)(M / G8_BM));
   auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(
-      (gemm_nt_8phase_kernel<G8_EPI_RELU_DOT, true, true, false>), grid,
-      dim3(G8_THREADS), 0, stream, (const bf16_t*)x.data_ptr(),
-      (const bf16_t*)w.data_ptr(), b2.data_ptr<float>(),
-      (const unsigned char*)w3.data_ptr<float>(), nullptr, y.data_ptr(),
-      M, N, K);
+#define L8_HEAD(LIVE_)                                                      \
+  hipLaunchKernelGGL(                                                       \
+      (gemm_nt_8phase_kernel<G8_EPI_RELU_DOT, true, true, false, LIVE_>),   \
+      grid, dim3(G8_THREADS), 0, stream, (const bf16_t*)x.data_ptr(),       \
+      (const bf16_t*)w.data_ptr(), b2.data_ptr<float>(),                    \
+      (const unsigned char*)w3.data_ptr<float>(), nullptr, y.data_ptr(), M, \
+      N, K, n_live)
+  if (n_live) L8_HEAD(true);
+  else        L8_HEAD(false);
+#undef L8_HEAD
   return y;
 }
 

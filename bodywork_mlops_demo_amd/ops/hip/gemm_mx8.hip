@@ -118,13 +118,19 @@ __device__ __forceinline__ void mx_stage_half(char* __restrict__ slot,
 // EMIT_MASK: also write the 1-bit ReLU mask of the produced activations
 // (uint8 [M, N/8], bit e of byte c = column 8c+e > 0 — the layout the
 // masked backward consumes, same emit as gemm8.hip's g8_epilogue).
-template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false>
+//
+// LIVE (RELU_DOT only): `live_rows` is the number of this tile's rows below
+// the device-side live row count (block-uniform, 1..MX_BM); rows at or past
+// it add nothing to y, so whatever their A rows hold never leaves the tile.
+template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false,
+          bool LIVE = false>
 __device__ __forceinline__ void mx_epilogue(
     mx_f32x4 (&acc)[4][4], const float* __restrict__ bias,
     const float* __restrict__ w3, unsigned char* __restrict__ mask_out,
     void* __restrict__ C, long long M, long long N, long long m0,
     long long n0, int wm, int wn, int fl, int kg,
-    const unsigned char* __restrict__ mask_in = nullptr) {
+    const unsigned char* __restrict__ mask_in = nullptr,
+    int live_rows = MX_BM) {
   if (EPI == MX_EPI_RELU_DOT) {
     // fused scoring head: y[row] += sum_col relu(acc + b2[col]) *
     // w3[col] — the h2 activation tensor is never materialised (saves
@@ -152,7 +158,9 @@ __device__ __forceinline__ void mx_epilogue(
 #pragma unroll
         for (int m = 1; m < 16; m <<= 1)
           part += __shfl_xor(part, m, 64);  // reduce across fl (lane&15)
-        if (fl == 0) {
+        // LIVE: a 32-bit compare of the row's place in the tile
+        if (fl == 0 &&
+            (!LIVE || wm * 64 + i * 16 + kg * 4 + r < live_rows)) {
           long long row = m0 + wm * 64 + i * 16 + kg * 4 + r;
           atomicAdd((float*)C + row, part);
         }
@@ -258,7 +266,7 @@ __global__ void quantize_e4m3_kernel(const T* __restrict__ x,
 
 template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false,
           int AFMT = MX_FMT_E4M3, int BFMT = MX_FMT_E4M3,
-          bool DEV_SCALE = false>
+          bool DEV_SCALE = false, bool LIVE = false>
 __launch_bounds__(MX_THREADS)
 __global__ void gemm_mx8_nt_1p_kernel(
     const unsigned char* __restrict__ A, const unsigned char* __restrict__ B,
@@ -267,10 +275,23 @@ __global__ void gemm_mx8_nt_1p_kernel(
     long long N, long long K, int sa, int sb,
     const int* __restrict__ ea_dev = nullptr,  // DEV_SCALE only
     const int* __restrict__ eb_dev = nullptr,
-    const unsigned char* __restrict__ mask_in = nullptr) {  // MASK_MUL only
+    const unsigned char* __restrict__ mask_in = nullptr,  // MASK_MUL only
+    const int64_t* __restrict__ n_live = nullptr) {       // LIVE only
   __shared__ char lds[10 * MX_HTB];  // A 2 slots + B 3 slots, 160 KB
   mx_dev_scales<DEV_SCALE>(sa, sb, ea_dev, eb_dev);
   const long long m0 = (long long)blockIdx.y * MX_BM;
+  // LIVE: a captured scoring graph keeps its bucket-sized grid and reads
+  // the request's row count (device int64[1], clamped to [0, M]) here.  A
+  // row tile past it returns before the first glds, barrier or LDS access;
+  // the test is block-uniform and the count stays in SGPRs.
+  int live_rows = MX_BM;
+  if constexpr (LIVE) {
+    static_assert(EPI == MX_EPI_RELU_DOT, "live rows: scoring head only");
+    long long live = (long long)*n_live;
+    live = live < 0 ? 0 : (live < M ? live : M);
+    if (m0 >= live) return;
+    live_rows = (int)(live - m0 < MX_BM ? live - m0 : MX_BM);
+  }
   const long long n0 = (long long)blockIdx.x * MX_BN;
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
@@ -403,8 +424,9 @@ __global__ void gemm_mx8_nt_1p_kernel(
 #undef P1_AR_BASE
 #undef P1_BR_BASE
 
-  mx_epilogue<EPI, HAS_BIAS, OUT_FP32, EMIT_MASK>(
-      acc, bias, w3, mask_out, C, M, N, m0, n0, wm, wn, fl, kg, mask_in);
+  mx_epilogue<EPI, HAS_BIAS, OUT_FP32, EMIT_MASK, LIVE>(
+      acc, bias, w3, mask_out, C, M, N, m0, n0, wm, wn, fl, kg, mask_in,
+      live_rows);
 }
 
 // ---- fused rank-1 expand -> e4m3 ------------------------------------------
@@ -419,7 +441,14 @@ __global__ void expand1d_e4m3_kernel(const float* __restrict__ x,
                                      const bf16_t* __restrict__ b,
                                      unsigned char* __restrict__ out,
                                      long long n, int h8 /* H/8 */,
-                                     float inv_scale) {
+                                     float inv_scale,
+                                     const int64_t* __restrict__ n_live) {
+  // n_live, when given, is the live row count (device int64[1], clamped to
+  // [0, n]): rows at or past it are neither read nor written
+  if (n_live != nullptr) {
+    long long live = (long long)*n_live;
+    n = live < 0 ? 0 : (live < n ? live : n);
+  }
   const long long total = (long long)n * h8;
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -696,11 +725,25 @@ __global__ void transpose_u8_kernel(const unsigned char* __restrict__ src,
 
 // ---- host wrappers --------------------------------------------------------
 
+// optional int64[1] live row count on the operand's device -> pointer
+// (nullptr when absent); the convention linear_score_hip set
+static const int64_t* mx_n_live_ptr(const c10::optional<at::Tensor>& n_dev,
+                                    const at::Tensor& like, const char* op) {
+  if (!n_dev.has_value() || !n_dev->defined()) return nullptr;
+  TORCH_CHECK(n_dev->is_cuda() && n_dev->device() == like.device() &&
+                  n_dev->numel() == 1 && n_dev->scalar_type() == at::kLong,
+              op, ": n_dev must be an int64[1] tensor on the operand's device");
+  return n_dev->data_ptr<int64_t>();
+}
+
+// n_dev: only the first n_dev rows are computed; the rest of the output
+// is left unwritten.
 at::Tensor expand1d_e4m3_hip(const at::Tensor& x, const at::Tensor& w,
-                             const c10::optional<at::Tensor>& b,
-                             int64_t e) {
+                             const c10::optional<at::Tensor>& b, int64_t e,
+                             const c10::optional<at::Tensor>& n_dev) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat);
   TORCH_CHECK(w.scalar_type() == at::kBFloat16);
+  const int64_t* n_live = mx_n_live_ptr(n_dev, x, "expand1d_e4m3");
   const long long n = x.numel();
   const long long H = w.numel();
   TORCH_CHECK(H % 8 == 0, "expand1d_e4m3: H must be a multiple of 8");
@@ -716,12 +759,12 @@ at::Tensor expand1d_e4m3_hip(const at::Tensor& x, const at::Tensor& w,
     hipLaunchKernelGGL((expand1d_e4m3_kernel<true>), dim3(grid), dim3(256),
                        0, stream, x.data_ptr<float>(), wp, bp,
                        out.data_ptr<unsigned char>(), n, (int)(H / 8),
-                       inv_scale);
+                       inv_scale, n_live);
   else
     hipLaunchKernelGGL((expand1d_e4m3_kernel<false>), dim3(grid), dim3(256),
                        0, stream, x.data_ptr<float>(), wp, bp,
                        out.data_ptr<unsigned char>(), n, (int)(H / 8),
-                       inv_scale);
+                       inv_scale, n_live);
   return out;
 }
 
@@ -807,6 +850,7 @@ struct MxGemm {
   const float* w3 = nullptr;          // RELU_DOT
   unsigned char* mask_out = nullptr;  // EMIT_MASK
   const unsigned char* mask_in = nullptr;  // MASK_MUL
+  const int64_t* n_live = nullptr;         // LIVE
   void* c = nullptr;
   bool empty() const { return M == 0 || N == 0; }  // nothing to launch
 };
@@ -858,14 +902,14 @@ static const float* mx_vec_n(const char* op, const char* what,
 
 template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false,
           int AFMT = MX_FMT_E4M3, int BFMT = MX_FMT_E4M3,
-          bool DEV_SCALE = false>
+          bool DEV_SCALE = false, bool LIVE = false>
 static void mx_launch(const MxGemm& g) {
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL((gemm_mx8_nt_1p_kernel<EPI, HAS_BIAS, OUT_FP32, EMIT_MASK,
-                                            AFMT, BFMT, DEV_SCALE>),
+                                            AFMT, BFMT, DEV_SCALE, LIVE>),
                      g.grid, dim3(MX_THREADS), 0, stream, g.a, g.b, g.bias,
                      g.w3, g.mask_out, g.c, g.M, g.N, g.K, g.sa, g.sb,
-                     g.ea_dev, g.eb_dev, g.mask_in);
+                     g.ea_dev, g.eb_dev, g.mask_in, g.n_live);
 }
 
 // C[M,N] = 2^(ea+eb) * (A[M,K]e4m3 . B[N,K]e4m3^T), optional fused
@@ -899,11 +943,12 @@ at::Tensor gemm_mx8_nt_hip(const at::Tensor& a8, int64_t ea,
 
 // y[M] = sum_col relu(a8.b8^T dequant + b2) * w3  — the MLP scoring
 // forward's h2 GEMM and rowdot head in ONE kernel: the [M,N] activation
-// tensor is never written to HBM.  Caller adds the scalar b3.
+// tensor is never written to HBM.  Caller adds the scalar b3.  With n_dev
+// the row tiles past that live count return at once and y[n_dev:] stays 0.
 at::Tensor gemm_mx8_relu_dot_hip(const at::Tensor& a8, int64_t ea,
                                  const at::Tensor& b8, int64_t eb,
-                                 const at::Tensor& b2,
-                                 const at::Tensor& w3) {
+                                 const at::Tensor& b2, const at::Tensor& w3,
+                                 const c10::optional<at::Tensor>& n_dev) {
   const char* op = "gemm_mx8_relu_dot";
   MxGemm g = mx_gemm_operands(op, a8, b8);
   g.sa = mx_e8m0(op, ea);
@@ -911,10 +956,15 @@ at::Tensor gemm_mx8_relu_dot_hip(const at::Tensor& a8, int64_t ea,
   g.bias = mx_vec_n(op, "b2", b2, g.N);
   g.w3 = mx_vec_n(op, "w3", w3, g.N);
   TORCH_CHECK(g.bias && g.w3, op, ": b2 and w3 are required");
+  g.n_live = mx_n_live_ptr(n_dev, a8, op);
   auto y = torch::zeros({g.M}, a8.options().dtype(torch::kFloat));
   if (g.empty()) return y;
   g.c = y.data_ptr();
-  mx_launch<MX_EPI_RELU_DOT, true, true>(g);
+  if (g.n_live)
+    mx_launch<MX_EPI_RELU_DOT, true, true, false, MX_FMT_E4M3, MX_FMT_E4M3,
+              false, true>(g);
+  else
+    mx_launch<MX_EPI_RELU_DOT, true, true>(g);
   return y;
 }
 

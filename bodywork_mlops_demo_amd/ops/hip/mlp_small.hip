@@ -21,14 +21,24 @@
 // c = column 8c+e > 0) — 16x less mask traffic than re-reading the bf16
 // activations, and the mask stays L2-resident at MLP scale.
 // EMIT_MASK: write that bitmask for the activations this kernel produces.
-template <bool RELU, bool HAS_BIAS, bool HAS_MASK, bool EMIT_MASK>
+// LIVE (plain scoring use: relu, no mask in or out): n_live is the live
+// row count (device int64[1], clamped to [0, n]); rows at or past it are
+// neither read nor written.
+template <bool RELU, bool HAS_BIAS, bool HAS_MASK, bool EMIT_MASK,
+          bool LIVE = false>
 __global__ void expand1d_kernel(const float* __restrict__ x,
                                 const bf16_t* __restrict__ w,
                                 const bf16_t* __restrict__ b,
                                 const unsigned char* __restrict__ mask,
                                 unsigned char* __restrict__ mask_out,
                                 bf16_t* __restrict__ out, long long n,
-                                int h8 /* H/8 */) {
+                                int h8 /* H/8 */,
+                                const int64_t* __restrict__ n_live = nullptr) {
+  if constexpr (LIVE) {
+    static_assert(RELU && !HAS_MASK && !EMIT_MASK, "live rows: scoring only");
+    long long live = (long long)*n_live;
+    n = live < 0 ? 0 : (live < n ? live : n);
+  }
   const long long total = (long long)n * h8;
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -62,9 +72,22 @@ __global__ void expand1d_kernel(const float* __restrict__ x,
 std::tuple<at::Tensor, at::Tensor> expand1d_bf16_hip(
     const at::Tensor& x, const at::Tensor& w,
     const c10::optional<at::Tensor>& b, bool relu,
-    const c10::optional<at::Tensor>& mask, bool emit_mask) {
+    const c10::optional<at::Tensor>& mask, bool emit_mask,
+    const c10::optional<at::Tensor>& n_dev) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat);
   TORCH_CHECK(w.scalar_type() == at::kBFloat16);
+  // n_dev (optional int64[1] device tensor): compute only the first n_dev
+  // rows and leave the rest of the output unwritten.  Scoring use only.
+  const int64_t* n_live = nullptr;
+  if (n_dev.has_value() && n_dev->defined()) {
+    TORCH_CHECK(n_dev->is_cuda() && n_dev->device() == x.device() &&
+                    n_dev->numel() == 1 && n_dev->scalar_type() == at::kLong,
+                "expand1d: n_dev must be an int64[1] tensor on x's device");
+    TORCH_CHECK(relu && !mask.has_value() && !emit_mask,
+                "expand1d: n_dev serves the plain relu scoring use only "
+                "(no mask, no emit_mask)");
+    n_live = n_dev->data_ptr<int64_t>();
+  }
   const long long n = x.numel();
   const long long H = w.numel();
   TORCH_CHECK(H % 8 == 0, "expand1d: H must be a multiple of 8");
@@ -97,7 +120,18 @@ std::tuple<at::Tensor, at::Tensor> expand1d_bf16_hip(
 #define LAUNCH_E1D_E(R, B_, M_)                                           \
   do { if (emit_mask) LAUNCH_E1D(R, B_, M_, true);                        \
        else LAUNCH_E1D(R, B_, M_, false); } while (0)
-  if (relu) {
+  if (n_live) {
+    if (has_bias)
+      hipLaunchKernelGGL((expand1d_kernel<true, true, false, false, true>),
+                         dim3(grid), dim3(256), 0, stream,
+                         x.data_ptr<float>(), wp, bp, mp, mop,
+                         (bf16_t*)out.data_ptr(), n, (int)(H / 8), n_live);
+    else
+      hipLaunchKernelGGL((expand1d_kernel<true, false, false, false, true>),
+                         dim3(grid), dim3(256), 0, stream,
+                         x.data_ptr<float>(), wp, bp, mp, mop,
+                         (bf16_t*)out.data_ptr(), n, (int)(H / 8), n_live);
+  } else if (relu) {
     if (has_bias) { if (has_mask) LAUNCH_E1D_E(true, true, true); else LAUNCH_E1D_E(true, true, false); }
     else          { if (has_mask) LAUNCH_E1D_E(true, false, true); else LAUNCH_E1D_E(true, false, false); }
   } else {

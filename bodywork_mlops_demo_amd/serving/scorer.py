@@ -10,11 +10,19 @@ sizes so the per-request launch overhead disappears from the hot loop
 Graph strategy: power-of-two batch buckets, one captured graph per
 bucket, static input/output buffers; a request is padded up to its
 bucket, replayed, and sliced.  Models whose kernels can read a live row
-count from device memory (``SUPPORTS_LIVE_ROWS``: the linear model) are
-not padded: the bucket keeps an int64 count tensor that is updated before
-each replay, and the captured kernel stops at that row.  Capture is lazy
-(first use of a bucket) and falls back to direct launches on CPU or when
-capture is unavailable.
+count from device memory (``SUPPORTS_LIVE_ROWS``: the linear model and
+the MLP) are not padded: the bucket keeps an int64 count tensor that is
+updated before each replay, and the captured kernels stop at that row.
+For the linear model that saves a pad fill; for the MLP it saves the
+GEMM work of the bucket's empty row tiles (the ladder's ratio is 16, so
+up to 16x): the graph keeps the bucket's grid, and every 256-row tile of
+the fused GEMM + relu + rowdot head past the count returns before it
+stages anything.  The MLP's 1- and 16-row buckets run kernels without
+tile gating and compute every row of the bucket; rows past the count
+hold whatever an earlier request left in the static input, and the
+result is sliced to the live rows as before.  The polynomial model keeps
+the pad-and-slice path.  Capture is lazy (first use of a bucket) and
+falls back to direct launches on CPU or when capture is unavailable.
 """
 from __future__ import annotations
 
