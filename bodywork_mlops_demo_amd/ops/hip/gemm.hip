@@ -21,19 +21,20 @@
 // read (both-sides rule; PMC-measured 0 bank conflicts); the fallback
 // register-staged kernels pad rows to 72 shorts (144-B stride) instead.
 // fp32 C/D per guide §3: col = lane&15, row = (lane>>4)*4 + reg.
+// The epilogue of a wave's 64x64 block (tile_epilogue, modes Epi::*) is
+// shared with gemm8.hip and gemm_mx8.hip: mfma_tile.h.
 #include <ATen/cuda/CUDAContext.h>
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 
 #include "bf16_utils.h"
+#include "mfma_tile.h"
 
 #define BM 128
 #define BN 128
 #define BK 64
 #define LDS_STRIDE 72  // BK + 8 shorts pad
 #define GEMM_THREADS 256
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 // stage a [ROWS x BK] K-major tile (row-major source, K contiguous):
 // thread t loads 16 B chunks; zero-fill outside (r1, k1) bounds.
@@ -94,97 +95,12 @@ __device__ __forceinline__ void stage_transposed(
   }
 }
 
-// epilogue modes
-#define EPI_NONE 0
-#define EPI_BIAS_RELU 1  // +bias then relu (bias may be null -> relu only)
-#define EPI_MASK 2       // multiply by (mask > 0)
-
-// shared epilogue: write the 4x4 fragment accumulator block.
-// EPI_MASK consumes a 1-BIT ReLU mask (uint8 [M, N/8], bit = col&7);
-// EMIT_MASK writes that bitmask for relu outputs (wave-ballot: the 16
-// lanes of a row-group supply the 16 bits, lane fl==0 stores a ushort).
-template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false>
-__device__ __forceinline__ void write_epilogue(
-    f32x4 (&acc)[4][4], const float* __restrict__ bias,
-    const unsigned char* __restrict__ mask,
-    unsigned char* __restrict__ mask_out, void* __restrict__ C, long long M,
-    long long N, long long m0, long long n0, int wm, int wn, int fl, int kg) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    // EPI_MASK: one aligned u64 per row covers this wave's whole 64-col
-    // stripe (bit b = col n0+wn*64+b) — replaces 16 scalar byte loads
-    unsigned long long mrow[4];
-    if (EPI == EPI_MASK) {
-      const long long stripe = n0 + wn * 64;
-      const bool full = stripe + 64 <= N;  // edge tile: byte-wise gather
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        long long row = m0 + wm * 64 + i * 16 + kg * 4 + r;
-        if (row >= M) {
-          mrow[r] = 0ull;
-        } else if (full) {
-          mrow[r] = *(const unsigned long long*)(mask + row * (N >> 3) +
-                                                 (stripe >> 3));
-        } else {
-          unsigned long long v = 0;
-          for (int b8 = 0; b8 < 8; ++b8)
-            if (stripe + b8 * 8 < N)
-              v |= (unsigned long long)
-                       mask[row * (N >> 3) + ((stripe >> 3) + b8)]
-                   << (8 * b8);
-          mrow[r] = v;
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      long long col = n0 + wn * 64 + j * 16 + fl;
-      bool col_ok = col < N;
-      float bval =
-          (EPI == EPI_BIAS_RELU && HAS_BIAS && col_ok) ? bias[col] : 0.0f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        long long row = m0 + wm * 64 + i * 16 + kg * 4 + r;
-        bool row_ok = row < M;
-        float v = acc[i][j][r];
-        if (EPI == EPI_BIAS_RELU) {
-          v += bval;
-          v = fmaxf(v, 0.0f);
-        } else if (EPI == EPI_MASK) {
-          v = (mrow[r] >> (j * 16 + fl)) & 1 ? v : 0.0f;
-        }
-        if (EMIT_MASK) {
-          // ballot over the wave: bits l of b = lane l's v>0; this
-          // row-group's 16 cols live at bits [kg*16, kg*16+16)
-          unsigned long long b = __ballot(v > 0.0f);
-          if (fl == 0 && row_ok && col < N) {
-            unsigned short bits = (unsigned short)((b >> (kg * 16)) & 0xFFFF);
-            *(unsigned short*)(mask_out + row * (N >> 3) + (col >> 3)) = bits;
-          }
-        }
-        if (row_ok && col_ok) {
-          if (OUT_FP32)
-            ((float*)C)[row * N + col] = v;
-          else
-            ((bf16_t*)C)[row * N + col] = f32_to_bf16(v);
-        }
-      }
-    }
-  }
-}
-
 // ---- glds-staged NT kernel (the hot path) --------------------------------
 // global_load_lds dwordx4 staging straight into a lane-linear LDS image;
 // the bank-conflict XOR swizzle lives on the SOURCE address and the
 // fragment-read address (both-sides rule): LDS chunk (row, c) holds the
 // logical 16-B chunk (row, c ^ (row & 7)).  Two LDS buffers, one
 // vmcnt(0)+barrier per K-tile (the guide's "step 3" structure).
-
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds(
-      (const __attribute__((address_space(1))) unsigned int*)gsrc,
-      (__attribute__((address_space(3))) unsigned int*)lds_dst, 16, 0, 0);
-}
 
 // stage a [128 x 64] bf16 tile: 16 wave-level 1-KiB glds per tile
 __device__ __forceinline__ void stage_tile_glds(
@@ -204,7 +120,7 @@ __device__ __forceinline__ void stage_tile_glds(
   }
 }
 
-template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false>
+template <Epi EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false>
 __launch_bounds__(GEMM_THREADS)
 __global__ void gemm_nt_glds_kernel(
     const bf16_t* __restrict__ A,  // [M,K]
@@ -275,11 +191,11 @@ __global__ void gemm_nt_glds_kernel(
     __syncthreads();  // drains next tile's glds; makes buffers reusable
     cur ^= 1;
   }
-  write_epilogue<EPI, HAS_BIAS, OUT_FP32, EMIT_MASK>(
-      acc, bias, mask, mask_out, C, M, N, m0, n0, wm, wn, fl, kg);
+  tile_epilogue<EPI, HAS_BIAS, OUT_FP32, EMIT_MASK>(
+      acc, bias, nullptr, mask, mask_out, C, M, N, m0, n0, wm, wn, fl, kg);
 }
 
-template <bool TN, int EPI, bool HAS_BIAS, bool OUT_FP32>
+template <bool TN, Epi EPI, bool HAS_BIAS, bool OUT_FP32>
 __launch_bounds__(GEMM_THREADS)
 __global__ void gemm_bf16_kernel(
     const bf16_t* __restrict__ A,  // NT: [M,K]; TN: [R=K, M]
@@ -334,13 +250,13 @@ __global__ void gemm_bf16_kernel(
     __syncthreads();
   }
 
-  write_epilogue<EPI, HAS_BIAS, OUT_FP32>(acc, bias, mask, nullptr, C, M, N,
-                                          m0, n0, wm, wn, fl, kg);
+  tile_epilogue<EPI, HAS_BIAS, OUT_FP32>(acc, bias, nullptr, mask, nullptr, C,
+                                         M, N, m0, n0, wm, wn, fl, kg);
 }
 
 // ---- launchers ------------------------------------------------------------
 
-static void launch_gemm(bool tn, int epi, bool has_bias, bool out_fp32,
+static void launch_gemm(bool tn, Epi epi, bool has_bias, bool out_fp32,
                         const at::Tensor& a, const at::Tensor& b,
                         const float* bias, const unsigned char* mask,
                         unsigned char* mask_out, at::Tensor& c,
@@ -363,10 +279,6 @@ static void launch_gemm(bool tn, int epi, bool has_bias, bool out_fp32,
       return (e && e[0] == '0') ? 0 : 1;
     }();
     if (use8) {
-      extern void launch_gemm8(int, bool, bool, bool, const void*,
-                               const void*, const float*,
-                               const unsigned char*, unsigned char*, void*,
-                               long long, long long, long long);
       launch_gemm8(epi, has_bias, out_fp32, mask_out != nullptr, ap, bp,
                    bias, mask, mask_out, cp, M, N, K);
       return;
@@ -380,22 +292,22 @@ static void launch_gemm(bool tn, int epi, bool has_bias, bool out_fp32,
   hipLaunchKernelGGL((gemm_nt_glds_kernel<EPI_, HB_, OF_, EM_>), grid,      \
                      dim3(GEMM_THREADS), 0, stream, ap, bp, bias, mask,     \
                      mask_out, cp, M, N, K)
-    if (epi == EPI_BIAS_RELU && mask_out != nullptr) {
-      if (has_bias) { if (out_fp32) G_GLDS(EPI_BIAS_RELU, true, true, true);
-                      else          G_GLDS(EPI_BIAS_RELU, true, false, true); }
-      else          { if (out_fp32) G_GLDS(EPI_BIAS_RELU, false, true, true);
-                      else          G_GLDS(EPI_BIAS_RELU, false, false, true); }
-    } else if (epi == EPI_BIAS_RELU) {
-      if (has_bias) { if (out_fp32) G_GLDS(EPI_BIAS_RELU, true, true, false);
-                      else          G_GLDS(EPI_BIAS_RELU, true, false, false); }
-      else          { if (out_fp32) G_GLDS(EPI_BIAS_RELU, false, true, false);
-                      else          G_GLDS(EPI_BIAS_RELU, false, false, false); }
-    } else if (epi == EPI_MASK) {
-      if (out_fp32) G_GLDS(EPI_MASK, false, true, false);
-      else          G_GLDS(EPI_MASK, false, false, false);
+    if (epi == Epi::BiasRelu && mask_out != nullptr) {
+      if (has_bias) { if (out_fp32) G_GLDS(Epi::BiasRelu, true, true, true);
+                      else          G_GLDS(Epi::BiasRelu, true, false, true); }
+      else          { if (out_fp32) G_GLDS(Epi::BiasRelu, false, true, true);
+                      else          G_GLDS(Epi::BiasRelu, false, false, true); }
+    } else if (epi == Epi::BiasRelu) {
+      if (has_bias) { if (out_fp32) G_GLDS(Epi::BiasRelu, true, true, false);
+                      else          G_GLDS(Epi::BiasRelu, true, false, false); }
+      else          { if (out_fp32) G_GLDS(Epi::BiasRelu, false, true, false);
+                      else          G_GLDS(Epi::BiasRelu, false, false, false); }
+    } else if (epi == Epi::MaskMul) {
+      if (out_fp32) G_GLDS(Epi::MaskMul, false, true, false);
+      else          G_GLDS(Epi::MaskMul, false, false, false);
     } else {
-      if (out_fp32) G_GLDS(EPI_NONE, false, true, false);
-      else          G_GLDS(EPI_NONE, false, false, false);
+      if (out_fp32) G_GLDS(Epi::None, false, true, false);
+      else          G_GLDS(Epi::None, false, false, false);
     }
 #undef G_GLDS
     return;
@@ -408,17 +320,17 @@ static void launch_gemm(bool tn, int epi, bool has_bias, bool out_fp32,
   /* mask_out unsupported on the fallback kernel (checked in hosts) */
 #define G_EPI(TN_)                                                          \
   do {                                                                      \
-    if (epi == EPI_BIAS_RELU) {                                             \
-      if (has_bias) { if (out_fp32) G_LAUNCH(TN_, EPI_BIAS_RELU, true, true);   \
-                      else          G_LAUNCH(TN_, EPI_BIAS_RELU, true, false); }\
-      else          { if (out_fp32) G_LAUNCH(TN_, EPI_BIAS_RELU, false, true);  \
-                      else          G_LAUNCH(TN_, EPI_BIAS_RELU, false, false);}\
-    } else if (epi == EPI_MASK) {                                           \
-      if (out_fp32) G_LAUNCH(TN_, EPI_MASK, false, true);                   \
-      else          G_LAUNCH(TN_, EPI_MASK, false, false);                  \
+    if (epi == Epi::BiasRelu) {                                             \
+      if (has_bias) { if (out_fp32) G_LAUNCH(TN_, Epi::BiasRelu, true, true);  \
+                      else          G_LAUNCH(TN_, Epi::BiasRelu, true, false); }\
+      else          { if (out_fp32) G_LAUNCH(TN_, Epi::BiasRelu, false, true); \
+                      else          G_LAUNCH(TN_, Epi::BiasRelu, false, false);}\
+    } else if (epi == Epi::MaskMul) {                                       \
+      if (out_fp32) G_LAUNCH(TN_, Epi::MaskMul, false, true);               \
+      else          G_LAUNCH(TN_, Epi::MaskMul, false, false);              \
     } else {                                                                \
-      if (out_fp32) G_LAUNCH(TN_, EPI_NONE, false, true);                   \
-      else          G_LAUNCH(TN_, EPI_NONE, false, false);                  \
+      if (out_fp32) G_LAUNCH(TN_, Epi::None, false, true);                  \
+      else          G_LAUNCH(TN_, Epi::None, false, false);                 \
     }                                                                       \
   } while (0)
   if (tn) G_EPI(true); else G_EPI(false);
@@ -445,10 +357,10 @@ at::Tensor linear_bf16_hip(const at::Tensor& x, const at::Tensor& w,
     bias_f = bias->to(at::kFloat);
     bp = bias_f.data_ptr<float>();
   }
-  int epi = mask.has_value() ? EPI_MASK
-            : (relu || bias.has_value()) ? EPI_BIAS_RELU
-                                         : EPI_NONE;
-  // bias without relu: fold via EPI_BIAS_RELU only when relu requested;
+  Epi epi = mask.has_value() ? Epi::MaskMul
+            : (relu || bias.has_value()) ? Epi::BiasRelu
+                                         : Epi::None;
+  // bias without relu: fold via Epi::BiasRelu only when relu requested;
   // else add bias in the same kernel without clamping -> use NONE + host
   // add would cost a pass, so clamp-free bias is handled here:
   TORCH_CHECK(!(bias.has_value() && !relu),
@@ -484,7 +396,7 @@ std::tuple<at::Tensor, at::Tensor> linear_relu_mask_bf16_hip(
     bias_f = bias->to(at::kFloat);
     bp = bias_f.data_ptr<float>();
   }
-  launch_gemm(false, EPI_BIAS_RELU, bias.has_value(), false, x, w, bp,
+  launch_gemm(false, Epi::BiasRelu, bias.has_value(), false, x, w, bp,
               nullptr, (unsigned char*)mask_out.data_ptr(), c, M, N, K);
   return {c, mask_out};
 }
@@ -499,7 +411,7 @@ at::Tensor gemm_tn_bf16_hip(const at::Tensor& a, const at::Tensor& b,
   TORCH_CHECK(b.size(0) == R, "gemm_tn: row counts must match");
   auto c = at::empty({M, N},
                      a.options().dtype(out_fp32 ? at::kFloat : at::kBFloat16));
-  launch_gemm(true, EPI_NONE, false, out_fp32, a, b, nullptr, nullptr,
+  launch_gemm(true, Epi::None, false, out_fp32, a, b, nullptr, nullptr,
               nullptr, c, M, N, R);
   return c;
 }

@@ -48,7 +48,11 @@
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 
+#include <type_traits>
+
 #include "bf16_utils.h"
+#include "host_checks.h"
+#include "mfma_tile.h"
 
 #define G8_BM 256
 #define G8_BN 256
@@ -56,25 +60,11 @@
 #define G8_THREADS 1024
 #define G8_HT (128 * 64)  // shorts per half-tile slot
 
-typedef __attribute__((ext_vector_type(4))) float g8_f32x4;
-
-#define G8_EPI_NONE 0
-#define G8_EPI_BIAS_RELU 1
-#define G8_EPI_MASK 2
-// fused scoring head: y[row] += sum_col relu(acc + bias[col]) * w3[col]
-// (the [M,N] activation never reaches HBM — mirrors gemm_mx8.hip's
-// MX_EPI_RELU_DOT).  In this mode the `mask` kernel argument carries
-// w3 (const float*) and C is y (fp32 [M], caller-zeroed).
-// LIVE (this epilogue only): the kernel reads a live row count from device
-// memory; row tiles past it return at once and rows at or past it add
-// nothing to y (same contract as gemm_mx8.hip's head).
-#define G8_EPI_RELU_DOT 3
-
-__device__ __forceinline__ void g8_glds16(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds(
-      (const __attribute__((address_space(1))) unsigned int*)gsrc,
-      (__attribute__((address_space(3))) unsigned int*)lds_dst, 16, 0, 0);
-}
+// The epilogue's read-only operand rides in ONE kernel-argument slot typed by
+// the mode: w3 (fp32 [N]) for the fused scoring head, else the 1-bit mask.
+template <Epi EPI>
+using EpiOperand = std::conditional_t<EPI == Epi::ReluDot, const float*,
+                                      const unsigned char*>;
 
 // stage one [128][64]-bf16 half-tile: 1024 16-B chunks, 1024 threads ->
 // ONE wave-level glds per wave.  Lane-linear LDS; XOR swizzle on the
@@ -87,132 +77,29 @@ __device__ __forceinline__ void g8_stage_half(short* __restrict__ slot,
                                               const char* __restrict__ base,
                                               int off0) {
   const int wave = threadIdx.x >> 6;
-  g8_glds16(base + off0, (char*)slot + wave * 1024);
+  glds16(base + off0, (char*)slot + wave * 1024);
 }
 
-template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK,
-          bool LIVE = false>
-__device__ __forceinline__ void g8_epilogue(
-    g8_f32x4 (&acc)[4][4], const float* __restrict__ bias,
-    const unsigned char* __restrict__ mask,
-    unsigned char* __restrict__ mask_out, void* __restrict__ C, long long M,
-    long long N, long long m0, long long n0, int wm, int wn, int fl, int kg,
-    int live_rows = G8_BM) {  // LIVE: this tile's rows below the live count
-  if (EPI == G8_EPI_RELU_DOT) {
-    const float* w3 = (const float*)mask;
-    float w3v[4], b2v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      long long col = n0 + wn * 64 + j * 16 + fl;
-      w3v[j] = w3[col];
-      b2v[j] = HAS_BIAS ? bias[col] : 0.0f;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float part = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          part = fmaf(fmaxf(acc[i][j][r] + b2v[j], 0.0f), w3v[j], part);
-#pragma unroll
-        for (int m = 1; m < 16; m <<= 1)
-          part += __shfl_xor(part, m, 64);  // reduce across fl (lane&15)
-        // LIVE: a 32-bit compare of the row's place in the tile
-        if (fl == 0 &&
-            (!LIVE || wm * 64 + i * 16 + kg * 4 + r < live_rows)) {
-          long long row = m0 + wm * 64 + i * 16 + kg * 4 + r;
-          atomicAdd((float*)C + row, part);
-        }
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    unsigned long long mrow[4];
-    if (EPI == G8_EPI_MASK) {
-      const long long stripe = n0 + wn * 64;
-      const bool full = stripe + 64 <= N;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        long long row = m0 + wm * 64 + i * 16 + kg * 4 + r;
-        if (row >= M) {
-          mrow[r] = 0ull;
-        } else if (full) {
-          mrow[r] = *(const unsigned long long*)(mask + row * (N >> 3) +
-                                                 (stripe >> 3));
-        } else {
-          unsigned long long v = 0;
-          for (int b8 = 0; b8 < 8; ++b8)
-            if (stripe + b8 * 8 < N)
-              v |= (unsigned long long)
-                       mask[row * (N >> 3) + ((stripe >> 3) + b8)]
-                   << (8 * b8);
-          mrow[r] = v;
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      long long col = n0 + wn * 64 + j * 16 + fl;
-      bool col_ok = col < N;
-      float bval =
-          (EPI == G8_EPI_BIAS_RELU && HAS_BIAS && col_ok) ? bias[col] : 0.0f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        long long row = m0 + wm * 64 + i * 16 + kg * 4 + r;
-        bool row_ok = row < M;
-        float v = acc[i][j][r];
-        if (EPI == G8_EPI_BIAS_RELU) {
-          v += bval;
-          v = fmaxf(v, 0.0f);
-        } else if (EPI == G8_EPI_MASK) {
-          v = (mrow[r] >> (j * 16 + fl)) & 1 ? v : 0.0f;
-        }
-        if (EMIT_MASK) {
-          unsigned long long b = __ballot(v > 0.0f);
-          if (fl == 0 && row_ok && col < N) {
-            unsigned short bits = (unsigned short)((b >> (kg * 16)) & 0xFFFF);
-            *(unsigned short*)(mask_out + row * (N >> 3) + (col >> 3)) = bits;
-          }
-        }
-        if (row_ok && col_ok) {
-          if (OUT_FP32)
-            ((float*)C)[row * N + col] = v;
-          else
-            ((bf16_t*)C)[row * N + col] = f32_to_bf16(v);
-        }
-      }
-    }
-  }
-}
-
-template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false,
+// LIVE (the scoring head only): row tiles at or past the device-side live
+// row count return at once and rows at or past it add nothing to y (same
+// contract as gemm_mx8.hip's head).
+template <Epi EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false,
           bool LIVE = false>
 __launch_bounds__(G8_THREADS)
 __global__ void gemm_nt_8phase_kernel(
     const bf16_t* __restrict__ A,  // [M,K]
     const bf16_t* __restrict__ B,  // [N,K]
-    const float* __restrict__ bias, const unsigned char* __restrict__ mask,
+    const float* __restrict__ bias, EpiOperand<EPI> __restrict__ epi_in,
     unsigned char* __restrict__ mask_out, void* __restrict__ C, long long M,
     long long N, long long K,
     const int64_t* __restrict__ n_live = nullptr) {  // LIVE only
   // ONE __shared__ object (guide §5 trap (a))
   __shared__ short lds[8 * G8_HT];  // [op A=0/B=1][buf][half][128][64]
   const long long m0 = (long long)blockIdx.y * G8_BM;
-  // LIVE: a captured scoring graph keeps its bucket-sized grid and reads
-  // the request's row count (device int64[1], clamped to [0, M]) here.  A
-  // row tile past it returns before the first glds, barrier or LDS access;
-  // the test is block-uniform and the count stays in SGPRs (the kernel has
-  // no VGPR to spare).
   int live_rows = G8_BM;
   if constexpr (LIVE) {
-    static_assert(EPI == G8_EPI_RELU_DOT, "live rows: scoring head only");
-    long long live = (long long)*n_live;
-    live = live < 0 ? 0 : (live < M ? live : M);
-    if (m0 >= live) return;
-    live_rows = (int)(live - m0 < G8_BM ? live - m0 : G8_BM);
+    static_assert(EPI == Epi::ReluDot, "live rows: scoring head only");
+    if (!tile_live_rows<G8_BM>(n_live, M, m0, live_rows)) return;
   }
   const long long n0 = (long long)blockIdx.x * G8_BN;
   const int wave = threadIdx.x >> 6;
@@ -233,7 +120,7 @@ __global__ void gemm_nt_8phase_kernel(
   const int a_inhalf = (wm & 1) * 64;
   const int b_inhalf = (wn & 1) * 64;
 
-  g8_f32x4 acc[4][4];
+  f32x4 acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -377,8 +264,13 @@ __global__ void gemm_nt_8phase_kernel(
 #undef G8_ASLOT
 #undef G8_BSLOT
 
-  g8_epilogue<EPI, HAS_BIAS, OUT_FP32, EMIT_MASK, LIVE>(
-      acc, bias, mask, mask_out, C, M, N, m0, n0, wm, wn, fl, kg, live_rows);
+  const float* w3 = nullptr;
+  const unsigned char* mask = nullptr;
+  if constexpr (EPI == Epi::ReluDot) w3 = epi_in;
+  else mask = epi_in;
+  tile_epilogue<EPI, HAS_BIAS, OUT_FP32, EMIT_MASK, LIVE>(
+      acc, bias, w3, mask, mask_out, C, M, N, m0, n0, wm, wn, fl, kg,
+      live_rows);
 }
 
 // y[M] = sum_col relu(x.w^T + b2) * w3 — the bf16 MLP scoring forward's
@@ -402,24 +294,16 @@ at::Tensor gemm8_relu_dot_bf16_hip(const at::Tensor& x, const at::Tensor& w,
                   b2.numel() == N, "b2: fp32 [N]");
   TORCH_CHECK(w3.is_cuda() && w3.scalar_type() == at::kFloat &&
                   w3.numel() == N, "w3: fp32 [N]");
-  const int64_t* n_live = nullptr;
-  if (n_dev.has_value() && n_dev->defined()) {
-    TORCH_CHECK(n_dev->is_cuda() && n_dev->device() == x.device() &&
-                    n_dev->numel() == 1 && n_dev->scalar_type() == at::kLong,
-                "gemm8_relu_dot: n_dev must be an int64[1] tensor on x's "
-                "device");
-    n_live = n_dev->data_ptr<int64_t>();
-  }
+  const int64_t* n_live = n_live_ptr(n_dev, x, "gemm8_relu_dot");
   auto y = at::zeros({M}, x.options().dtype(at::kFloat));
   dim3 grid((unsigned)(N / G8_BN), (unsigned)(M / G8_BM));
   auto stream = at::cuda::getCurrentCUDAStream();
 #define L8_HEAD(LIVE_)                                                      \
   hipLaunchKernelGGL(                                                       \
-      (gemm_nt_8phase_kernel<G8_EPI_RELU_DOT, true, true, false, LIVE_>),   \
+      (gemm_nt_8phase_kernel<Epi::ReluDot, true, true, false, LIVE_>),      \
       grid, dim3(G8_THREADS), 0, stream, (const bf16_t*)x.data_ptr(),       \
       (const bf16_t*)w.data_ptr(), b2.data_ptr<float>(),                    \
-      (const unsigned char*)w3.data_ptr<float>(), nullptr, y.data_ptr(), M, \
-      N, K, n_live)
+      w3.data_ptr<float>(), nullptr, y.data_ptr(), M, N, K, n_live)
   if (n_live) L8_HEAD(true);
   else        L8_HEAD(false);
 #undef L8_HEAD
@@ -427,7 +311,7 @@ at::Tensor gemm8_relu_dot_bf16_hip(const at::Tensor& x, const at::Tensor& w,
 }
 
 // ---- launcher (called from gemm.hip's dispatch) ---------------------------
-void launch_gemm8(int epi, bool has_bias, bool out_fp32, bool emit_mask,
+void launch_gemm8(Epi epi, bool has_bias, bool out_fp32, bool emit_mask,
                   const void* ap, const void* bp, const float* bias,
                   const unsigned char* mask, unsigned char* mask_out,
                   void* cp, long long M, long long N, long long K) {
@@ -440,20 +324,20 @@ void launch_gemm8(int epi, bool has_bias, bool out_fp32, bool emit_mask,
   hipLaunchKernelGGL((gemm_nt_8phase_kernel<EPI_, HB_, OF_, EM_>), grid,    \
                      dim3(G8_THREADS), 0, stream, a, b, bias, mask,         \
                      mask_out, cp, M, N, K)
-  if (epi == G8_EPI_BIAS_RELU && emit_mask) {
-    if (has_bias) L8(G8_EPI_BIAS_RELU, true, false, true);
-    else          L8(G8_EPI_BIAS_RELU, false, false, true);
-  } else if (epi == G8_EPI_BIAS_RELU) {
-    if (has_bias) { if (out_fp32) L8(G8_EPI_BIAS_RELU, true, true, false);
-                    else          L8(G8_EPI_BIAS_RELU, true, false, false); }
-    else          { if (out_fp32) L8(G8_EPI_BIAS_RELU, false, true, false);
-                    else          L8(G8_EPI_BIAS_RELU, false, false, false); }
-  } else if (epi == G8_EPI_MASK) {
-    if (out_fp32) L8(G8_EPI_MASK, false, true, false);
-    else          L8(G8_EPI_MASK, false, false, false);
+  if (epi == Epi::BiasRelu && emit_mask) {
+    if (has_bias) L8(Epi::BiasRelu, true, false, true);
+    else          L8(Epi::BiasRelu, false, false, true);
+  } else if (epi == Epi::BiasRelu) {
+    if (has_bias) { if (out_fp32) L8(Epi::BiasRelu, true, true, false);
+                    else          L8(Epi::BiasRelu, true, false, false); }
+    else          { if (out_fp32) L8(Epi::BiasRelu, false, true, false);
+                    else          L8(Epi::BiasRelu, false, false, false); }
+  } else if (epi == Epi::MaskMul) {
+    if (out_fp32) L8(Epi::MaskMul, false, true, false);
+    else          L8(Epi::MaskMul, false, false, false);
   } else {
-    if (out_fp32) L8(G8_EPI_NONE, false, true, false);
-    else          L8(G8_EPI_NONE, false, false, false);
+    if (out_fp32) L8(Epi::None, false, true, false);
+    else          L8(Epi::None, false, false, false);
   }
 #undef L8
 }

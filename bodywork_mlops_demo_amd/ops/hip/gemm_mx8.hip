@@ -55,7 +55,7 @@
 // formats are one byte so the memory system is unchanged), either
 // exponent may carry a per-step part read from device memory before the
 // K-loop (so a captured step graph follows the gradient scale), and the
-// MX_EPI_MASK_MUL epilogue applies a 1-bit ReLU mask (dz1 = ... * m1).
+// Epi::MaskMul epilogue applies a 1-bit ReLU mask (dz1 = ... * m1).
 //
 // The reference computes its scoring forward in fp64 sklearn
 // (stage_2_serve_model.py:78); this kernel is the opt-in low-precision
@@ -65,6 +65,9 @@
 #include <torch/extension.h>
 
 #include "bf16_utils.h"
+#include "expand1d.h"
+#include "host_checks.h"
+#include "mfma_tile.h"
 
 #define MX_BM 256
 #define MX_BN 256
@@ -74,12 +77,6 @@
 
 typedef __attribute__((ext_vector_type(8))) int mx_i32x8;
 typedef __attribute__((ext_vector_type(4))) int mx_i32x4;
-typedef __attribute__((ext_vector_type(4))) float mx_f32x4;
-
-#define MX_EPI_NONE 0
-#define MX_EPI_BIAS_RELU 1
-#define MX_EPI_RELU_DOT 2  // y[row] += sum_col relu(acc+bias)*w3[col]
-#define MX_EPI_MASK_MUL 3  // C = acc * bit(mask_in[row, col]) (ReLU backward)
 
 // operand formats = the scaled MFMA's cbsz (A) / blgp (B) immediates
 #define MX_FMT_E4M3 0
@@ -100,126 +97,13 @@ __device__ __forceinline__ void mx_dev_scales(int& sa, int& sb,
   }
 }
 
-__device__ __forceinline__ void mx_glds16(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds(
-      (const __attribute__((address_space(1))) unsigned int*)gsrc,
-      (__attribute__((address_space(3))) unsigned int*)lds_dst, 16, 0, 0);
-}
-
 // stage one [128 rows][128 B] half-tile: 1024 16-B chunks, 1024 threads
 // -> ONE wave-level glds per wave (identical to gemm8's g8_stage_half).
 __device__ __forceinline__ void mx_stage_half(char* __restrict__ slot,
                                               const char* __restrict__ base,
                                               int off0) {
   const int wave = threadIdx.x >> 6;
-  mx_glds16(base + off0, slot + wave * 1024);
-}
-
-// EMIT_MASK: also write the 1-bit ReLU mask of the produced activations
-// (uint8 [M, N/8], bit e of byte c = column 8c+e > 0 — the layout the
-// masked backward consumes, same emit as gemm8.hip's g8_epilogue).
-//
-// LIVE (RELU_DOT only): `live_rows` is the number of this tile's rows below
-// the device-side live row count (block-uniform, 1..MX_BM); rows at or past
-// it add nothing to y, so whatever their A rows hold never leaves the tile.
-template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false,
-          bool LIVE = false>
-__device__ __forceinline__ void mx_epilogue(
-    mx_f32x4 (&acc)[4][4], const float* __restrict__ bias,
-    const float* __restrict__ w3, unsigned char* __restrict__ mask_out,
-    void* __restrict__ C, long long M, long long N, long long m0,
-    long long n0, int wm, int wn, int fl, int kg,
-    const unsigned char* __restrict__ mask_in = nullptr,
-    int live_rows = MX_BM) {
-  if (EPI == MX_EPI_RELU_DOT) {
-    // fused scoring head: y[row] += sum_col relu(acc + b2[col]) *
-    // w3[col] — the h2 activation tensor is never materialised (saves
-    // its [M,N] bf16 write + the rowdot re-read, ~16 GB of HBM per 1M
-    // rows at N=4096).  Per (i,r) row: 16 lanes (fl) x 4 j-frags hold
-    // the wave's 64-column strip; butterfly-reduce across fl, then the
-    // fl==0 lane of each kg row atomically adds its wave's partial
-    // (4 wn-waves per block and N/256 blocks accumulate per row; the
-    // caller zero-fills y and adds the b3 offset).
-    float w3v[4], b2v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      long long col = n0 + wn * 64 + j * 16 + fl;
-      w3v[j] = w3[col];
-      b2v[j] = HAS_BIAS ? bias[col] : 0.0f;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float part = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          part = fmaf(fmaxf(acc[i][j][r] + b2v[j], 0.0f), w3v[j], part);
-#pragma unroll
-        for (int m = 1; m < 16; m <<= 1)
-          part += __shfl_xor(part, m, 64);  // reduce across fl (lane&15)
-        // LIVE: a 32-bit compare of the row's place in the tile
-        if (fl == 0 &&
-            (!LIVE || wm * 64 + i * 16 + kg * 4 + r < live_rows)) {
-          long long row = m0 + wm * 64 + i * 16 + kg * 4 + r;
-          atomicAdd((float*)C + row, part);
-        }
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    // MASK_MUL: the wave's 64-column strip of a row is ONE 8-byte mask
-    // word (N % 256 == 0, so strips are whole and 8-byte aligned); read
-    // here, after the accumulators are final, as g8_epilogue does
-    unsigned long long mrow[4];
-    if (EPI == MX_EPI_MASK_MUL) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        long long row = m0 + wm * 64 + i * 16 + kg * 4 + r;
-        mrow[r] = row < M ? *(const unsigned long long*)(mask_in +
-                                                         row * (N >> 3) +
-                                                         ((n0 + wn * 64) >> 3))
-                          : 0ull;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      long long col = n0 + wn * 64 + j * 16 + fl;
-      bool col_ok = col < N;
-      float bval =
-          (EPI == MX_EPI_BIAS_RELU && HAS_BIAS && col_ok) ? bias[col] : 0.0f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        long long row = m0 + wm * 64 + i * 16 + kg * 4 + r;
-        float v = acc[i][j][r];
-        if (EPI == MX_EPI_BIAS_RELU) {
-          v += bval;
-          v = fmaxf(v, 0.0f);
-        } else if (EPI == MX_EPI_MASK_MUL) {
-          v = (mrow[r] >> (j * 16 + fl)) & 1 ? v : 0.0f;
-        }
-        if (EMIT_MASK) {
-          // wave-wide ballot OUTSIDE the row/col conditional; lane
-          // kg*16+fl holds (row of kg, col fl), so each kg group's 16-bit
-          // slice is two consecutive mask bytes of its row
-          unsigned long long bal = __ballot(v > 0.0f);
-          if (fl == 0 && row < M && col_ok) {
-            unsigned short bits =
-                (unsigned short)((bal >> (kg * 16)) & 0xFFFF);
-            *(unsigned short*)(mask_out + row * (N >> 3) + (col >> 3)) = bits;
-          }
-        }
-        if (row < M && col_ok) {
-          if (OUT_FP32)
-            ((float*)C)[row * N + col] = v;
-          else
-            ((bf16_t*)C)[row * N + col] = f32_to_bf16(v);
-        }
-      }
-    }
-  }
+  glds16(base + off0, slot + wave * 1024);
 }
 
 // ---- per-tensor e4m3 quantisation ----------------------------------------
@@ -264,7 +148,7 @@ __global__ void quantize_e4m3_kernel(const T* __restrict__ x,
 #define P1_BSLOT(buf, half) (lds + (4 + (buf) * 2 + (half)) * MX_HTB)
 #define MX_KOFF(T) ((long long)(T) * MX_BK)  // byte offset of K-tile T in a row
 
-template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false,
+template <Epi EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false,
           int AFMT = MX_FMT_E4M3, int BFMT = MX_FMT_E4M3,
           bool DEV_SCALE = false, bool LIVE = false>
 __launch_bounds__(MX_THREADS)
@@ -280,17 +164,10 @@ __global__ void gemm_mx8_nt_1p_kernel(
   __shared__ char lds[10 * MX_HTB];  // A 2 slots + B 3 slots, 160 KB
   mx_dev_scales<DEV_SCALE>(sa, sb, ea_dev, eb_dev);
   const long long m0 = (long long)blockIdx.y * MX_BM;
-  // LIVE: a captured scoring graph keeps its bucket-sized grid and reads
-  // the request's row count (device int64[1], clamped to [0, M]) here.  A
-  // row tile past it returns before the first glds, barrier or LDS access;
-  // the test is block-uniform and the count stays in SGPRs.
   int live_rows = MX_BM;
   if constexpr (LIVE) {
-    static_assert(EPI == MX_EPI_RELU_DOT, "live rows: scoring head only");
-    long long live = (long long)*n_live;
-    live = live < 0 ? 0 : (live < M ? live : M);
-    if (m0 >= live) return;
-    live_rows = (int)(live - m0 < MX_BM ? live - m0 : MX_BM);
+    static_assert(EPI == Epi::ReluDot, "live rows: scoring head only");
+    if (!tile_live_rows<MX_BM>(n_live, M, m0, live_rows)) return;
   }
   const long long n0 = (long long)blockIdx.x * MX_BN;
   const int wave = threadIdx.x >> 6;
@@ -312,7 +189,7 @@ __global__ void gemm_mx8_nt_1p_kernel(
   const int a_inhalf = (wm & 1) * 64;
   const int b_inhalf = (wn & 1) * 64;
 
-  mx_f32x4 acc[4][4];
+  f32x4 acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -424,8 +301,9 @@ __global__ void gemm_mx8_nt_1p_kernel(
 #undef P1_AR_BASE
 #undef P1_BR_BASE
 
-  mx_epilogue<EPI, HAS_BIAS, OUT_FP32, EMIT_MASK, LIVE>(
-      acc, bias, w3, mask_out, C, M, N, m0, n0, wm, wn, fl, kg, mask_in,
+  // N % 256 == 0: every wave's mask stripe is whole (WHOLE_STRIPES)
+  tile_epilogue<EPI, HAS_BIAS, OUT_FP32, EMIT_MASK, LIVE, true>(
+      acc, bias, w3, mask_in, mask_out, C, M, N, m0, n0, wm, wn, fl, kg,
       live_rows);
 }
 
@@ -445,34 +323,12 @@ __global__ void expand1d_e4m3_kernel(const float* __restrict__ x,
                                      const int64_t* __restrict__ n_live) {
   // n_live, when given, is the live row count (device int64[1], clamped to
   // [0, n]): rows at or past it are neither read nor written
-  if (n_live != nullptr) {
-    long long live = (long long)*n_live;
-    n = live < 0 ? 0 : (live < n ? live : n);
-  }
-  const long long total = (long long)n * h8;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       idx < total; idx += stride) {
-    const long long row = idx / h8;
-    const int c8 = (int)(idx % h8);
-    float xv = x[row];
-    float wv[8], bv[8];
-    bf16x8_to_f32(load_bf16x8(w + c8 * 8), wv);
-    if (HAS_BIAS) bf16x8_to_f32(load_bf16x8(b + c8 * 8), bv);
-    unsigned long long packed = 0;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      float a0 = HAS_BIAS ? fmaf(xv, wv[2 * p], bv[2 * p]) : xv * wv[2 * p];
-      float a1 = HAS_BIAS ? fmaf(xv, wv[2 * p + 1], bv[2 * p + 1])
-                          : xv * wv[2 * p + 1];
-      a0 = fmaxf(a0, 0.0f) * inv_scale;  // relu fused
-      a1 = fmaxf(a1, 0.0f) * inv_scale;
-      unsigned int pk = (unsigned int)
-          __builtin_amdgcn_cvt_pk_fp8_f32(a0, a1, 0, false);
-      packed |= (unsigned long long)(pk & 0xFFFFu) << (16 * p);
-    }
-    *(unsigned long long*)(out + row * (long long)h8 * 8 + c8 * 8) = packed;
-  }
+  if (n_live != nullptr) n = live_count(n_live, n);
+  e1d_for_each_chunk(n, h8, [&](long long row, int c8) {
+    float acc[8];
+    e1d_axpb<true, HAS_BIAS>(x[row], w, b, c8, acc);
+    e1d_store_e4m3(out, e1d_offset(row, h8, c8), acc, inv_scale);
+  });
 }
 
 // ---- dual-emit rank-1 expand: bf16 + 1-bit mask + e4m3 --------------------
@@ -490,55 +346,20 @@ __global__ void expand1d_bf16_e4m3_kernel(
     const bf16_t* __restrict__ b, bf16_t* __restrict__ out,
     unsigned char* __restrict__ mask_out, unsigned char* __restrict__ out8,
     long long n, int h8 /* H/8 */, float inv_scale) {
-  const long long total = (long long)n * h8;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       idx < total; idx += stride) {
-    const long long row = idx / h8;
-    const int c8 = (int)(idx % h8);
-    float xv = x[row];
-    float wv[8], bv[8], acc[8];
-    bf16x8_to_f32(load_bf16x8(w + c8 * 8), wv);
-    if (HAS_BIAS) bf16x8_to_f32(load_bf16x8(b + c8 * 8), bv);
-    unsigned char mb = 0;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      acc[e] = HAS_BIAS ? fmaf(xv, wv[e], bv[e]) : xv * wv[e];
-      acc[e] = fmaxf(acc[e], 0.0f);
-      mb |= (acc[e] > 0.0f ? 1u : 0u) << e;
-    }
-    unsigned long long packed = 0;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      unsigned int pk = (unsigned int)__builtin_amdgcn_cvt_pk_fp8_f32(
-          acc[2 * p] * inv_scale, acc[2 * p + 1] * inv_scale, 0, false);
-      packed |= (unsigned long long)(pk & 0xFFFFu) << (16 * p);
-    }
-    const long long o = row * (long long)h8 * 8 + c8 * 8;
-    mask_out[row * h8 + c8] = mb;
-    store_bf16x8(out + o, f32_to_bf16x8(acc));
-    *(unsigned long long*)(out8 + o) = packed;
-  }
+  e1d_for_each_chunk(n, h8, [&](long long row, int c8) {
+    float acc[8];
+    e1d_axpb<true, HAS_BIAS>(x[row], w, b, c8, acc);
+    const long long o = e1d_offset(row, h8, c8);
+    mask_out[row * h8 + c8] = e1d_mask_bits(acc);
+    e1d_store_bf16(out, o, acc);
+    e1d_store_e4m3(out8, o, acc, inv_scale);
+  });
 }
 
 // ---- e5m2 (gradient format) support kernels -------------------------------
 //
-// OCP e5m2 (S.EEEEE.MM, bias 15, max finite 57344, inf at 0x7C).  The
-// scaled value is clamped to +-57344 in plain code BEFORE the packed
-// convert, so saturation is defined here and never by the instruction's
-// overflow mode; NaN passes through the comparisons unchanged.
-__device__ __forceinline__ float mx_e5m2_prescale(float v, int e) {
-  v = ldexpf(v, -e);  // exact power-of-two scaling for any e in [-127,127]
-  v = v > 57344.0f ? 57344.0f : v;
-  v = v < -57344.0f ? -57344.0f : v;
-  return v;
-}
-
-// two floats -> two e5m2 bytes (RNE) in the low 16 bits
-__device__ __forceinline__ unsigned int mx_cvt2_e5m2(float v0, float v1) {
-  return (unsigned int)__builtin_amdgcn_cvt_pk_bf8_f32(v0, v1, 0, false) &
-         0xFFFFu;
-}
+// mx_e5m2_prescale and mx_cvt2_e5m2 (the defined-saturation RNE convert) are
+// in expand1d.h.
 
 // Per-step gradient exponent, computed on the device so a captured step
 // never syncs: a = max|x| * max|w| (fp32) bounds every |x[i]*w[j]|
@@ -635,34 +456,14 @@ __global__ void expand1d_bf16_e5m2_kernel(
     bf16_t* __restrict__ out, unsigned char* __restrict__ out8, long long n,
     int h8 /* H/8 */) {
   const int e = *e_dev;
-  const long long total = (long long)n * h8;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       idx < total; idx += stride) {
-    const long long row = idx / h8;
-    const int c8 = (int)(idx % h8);
-    float xv = x[row];
-    float wv[8], acc[8], rb[8];
-    bf16x8_to_f32(load_bf16x8(w + c8 * 8), wv);
-    unsigned char mb = mask[row * h8 + c8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      acc[k] = xv * wv[k];
-      acc[k] = (mb >> k) & 1 ? acc[k] : 0.0f;
-    }
-    const bf16x8 ob = f32_to_bf16x8(acc);
-    bf16x8_to_f32(ob, rb);
-    unsigned long long packed = 0;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      unsigned int pk = mx_cvt2_e5m2(mx_e5m2_prescale(rb[2 * p], e),
-                                     mx_e5m2_prescale(rb[2 * p + 1], e));
-      packed |= (unsigned long long)pk << (16 * p);
-    }
-    const long long o = row * (long long)h8 * 8 + c8 * 8;
-    store_bf16x8(out + o, ob);
-    *(unsigned long long*)(out8 + o) = packed;
-  }
+  e1d_for_each_chunk(n, h8, [&](long long row, int c8) {
+    float acc[8], rb[8];
+    e1d_axpb<false, false>(x[row], w, nullptr, c8, acc);
+    e1d_apply_mask(mask[row * h8 + c8], acc);
+    const long long o = e1d_offset(row, h8, c8);
+    bf16x8_to_f32(e1d_store_bf16(out, o, acc), rb);
+    e1d_store_e5m2(out8, o, rb, e);
+  });
 }
 
 // Byte transpose dst[C,R] = src[R,C]^T for the wgrad operands (both must
@@ -725,85 +526,47 @@ __global__ void transpose_u8_kernel(const unsigned char* __restrict__ src,
 
 // ---- host wrappers --------------------------------------------------------
 
-// optional int64[1] live row count on the operand's device -> pointer
-// (nullptr when absent); the convention linear_score_hip set
-static const int64_t* mx_n_live_ptr(const c10::optional<at::Tensor>& n_dev,
-                                    const at::Tensor& like, const char* op) {
-  if (!n_dev.has_value() || !n_dev->defined()) return nullptr;
-  TORCH_CHECK(n_dev->is_cuda() && n_dev->device() == like.device() &&
-                  n_dev->numel() == 1 && n_dev->scalar_type() == at::kLong,
-              op, ": n_dev must be an int64[1] tensor on the operand's device");
-  return n_dev->data_ptr<int64_t>();
-}
-
 // n_dev: only the first n_dev rows are computed; the rest of the output
 // is left unwritten.
 at::Tensor expand1d_e4m3_hip(const at::Tensor& x, const at::Tensor& w,
                              const c10::optional<at::Tensor>& b, int64_t e,
                              const c10::optional<at::Tensor>& n_dev) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat);
-  TORCH_CHECK(w.scalar_type() == at::kBFloat16);
-  const int64_t* n_live = mx_n_live_ptr(n_dev, x, "expand1d_e4m3");
-  const long long n = x.numel();
-  const long long H = w.numel();
-  TORCH_CHECK(H % 8 == 0, "expand1d_e4m3: H must be a multiple of 8");
-  auto out = at::empty({n, H}, w.options().dtype(at::kByte));
-  const bool has_bias = b.has_value();
+  const Expand1dArgs a = expand1d_args("expand1d_e4m3", x, w, b);
+  const int64_t* n_live = n_live_ptr(n_dev, x, "expand1d_e4m3");
+  auto out = at::empty({a.n, a.H}, w.options().dtype(at::kByte));
+  if (a.grid == 0) return out;
   auto stream = at::cuda::getCurrentCUDAStream();
-  long long total = n * (H / 8);
-  int grid = (int)std::min<long long>((total + 255) / 256, 2048);
   float inv_scale = ldexpf(1.0f, (int)-e);
-  const bf16_t* wp = (const bf16_t*)w.data_ptr();
-  const bf16_t* bp = has_bias ? (const bf16_t*)b->data_ptr() : nullptr;
-  if (has_bias)
-    hipLaunchKernelGGL((expand1d_e4m3_kernel<true>), dim3(grid), dim3(256),
-                       0, stream, x.data_ptr<float>(), wp, bp,
-                       out.data_ptr<unsigned char>(), n, (int)(H / 8),
-                       inv_scale, n_live);
-  else
-    hipLaunchKernelGGL((expand1d_e4m3_kernel<false>), dim3(grid), dim3(256),
-                       0, stream, x.data_ptr<float>(), wp, bp,
-                       out.data_ptr<unsigned char>(), n, (int)(H / 8),
-                       inv_scale, n_live);
+#define LAUNCH_E1D_E4M3(B_)                                                 \
+  hipLaunchKernelGGL((expand1d_e4m3_kernel<B_>), dim3(a.grid), dim3(256),   \
+                     0, stream, a.x, a.w, a.b,                              \
+                     out.data_ptr<unsigned char>(), a.n, a.h8, inv_scale,   \
+                     n_live)
+  if (a.b) LAUNCH_E1D_E4M3(true);
+  else     LAUNCH_E1D_E4M3(false);
+#undef LAUNCH_E1D_E4M3
   return out;
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor> expand1d_bf16_e4m3_hip(
     const at::Tensor& x, const at::Tensor& w,
     const c10::optional<at::Tensor>& b, int64_t e) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat);
-  TORCH_CHECK(w.scalar_type() == at::kBFloat16);
-  const long long n = x.numel();
-  const long long H = w.numel();
-  TORCH_CHECK(H % 8 == 0, "expand1d_bf16_e4m3: H must be a multiple of 8");
-  const bool has_bias = b.has_value();
-  if (has_bias)
-    TORCH_CHECK(b->scalar_type() == at::kBFloat16 && b->numel() == H,
-                "expand1d_bf16_e4m3: bias must be bf16 [H]");
-  auto out = at::empty({n, H}, w.options());
-  auto mask_out = at::empty({n, H / 8}, w.options().dtype(at::kByte));
-  auto out8 = at::empty({n, H}, w.options().dtype(at::kByte));
+  const Expand1dArgs a = expand1d_args("expand1d_bf16_e4m3", x, w, b);
+  auto out = at::empty({a.n, a.H}, w.options());
+  auto mask_out = at::empty({a.n, a.H / 8}, w.options().dtype(at::kByte));
+  auto out8 = at::empty({a.n, a.H}, w.options().dtype(at::kByte));
+  if (a.grid == 0) return {out, mask_out, out8};
   auto stream = at::cuda::getCurrentCUDAStream();
-  long long total = n * (H / 8);
-  if (total == 0) return {out, mask_out, out8};
-  int grid = (int)std::min<long long>((total + 255) / 256, 2048);
   float inv_scale = ldexpf(1.0f, (int)-e);
-  const bf16_t* wp = (const bf16_t*)w.data_ptr();
-  const bf16_t* bp = has_bias ? (const bf16_t*)b->data_ptr() : nullptr;
-  if (has_bias)
-    hipLaunchKernelGGL((expand1d_bf16_e4m3_kernel<true>), dim3(grid),
-                       dim3(256), 0, stream, x.data_ptr<float>(), wp, bp,
-                       (bf16_t*)out.data_ptr(),
-                       mask_out.data_ptr<unsigned char>(),
-                       out8.data_ptr<unsigned char>(), n, (int)(H / 8),
-                       inv_scale);
-  else
-    hipLaunchKernelGGL((expand1d_bf16_e4m3_kernel<false>), dim3(grid),
-                       dim3(256), 0, stream, x.data_ptr<float>(), wp, bp,
-                       (bf16_t*)out.data_ptr(),
-                       mask_out.data_ptr<unsigned char>(),
-                       out8.data_ptr<unsigned char>(), n, (int)(H / 8),
-                       inv_scale);
+#define LAUNCH_E1D_BF16_E4M3(B_)                                            \
+  hipLaunchKernelGGL((expand1d_bf16_e4m3_kernel<B_>), dim3(a.grid),         \
+                     dim3(256), 0, stream, a.x, a.w, a.b,                   \
+                     (bf16_t*)out.data_ptr(),                               \
+                     mask_out.data_ptr<unsigned char>(),                    \
+                     out8.data_ptr<unsigned char>(), a.n, a.h8, inv_scale)
+  if (a.b) LAUNCH_E1D_BF16_E4M3(true);
+  else     LAUNCH_E1D_BF16_E4M3(false);
+#undef LAUNCH_E1D_BF16_E4M3
   return {out, mask_out, out8};
 }
 
@@ -900,7 +663,7 @@ static const float* mx_vec_n(const char* op, const char* what,
   return v->data_ptr<float>();
 }
 
-template <int EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false,
+template <Epi EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false,
           int AFMT = MX_FMT_E4M3, int BFMT = MX_FMT_E4M3,
           bool DEV_SCALE = false, bool LIVE = false>
 static void mx_launch(const MxGemm& g) {
@@ -929,14 +692,14 @@ at::Tensor gemm_mx8_nt_hip(const at::Tensor& a8, int64_t ea,
   if (g.empty()) return C;
   g.c = C.data_ptr();
   if (!relu) {
-    if (out_fp32) mx_launch<MX_EPI_NONE, false, true>(g);
-    else          mx_launch<MX_EPI_NONE, false, false>(g);
+    if (out_fp32) mx_launch<Epi::None, false, true>(g);
+    else          mx_launch<Epi::None, false, false>(g);
   } else if (g.bias) {
-    if (out_fp32) mx_launch<MX_EPI_BIAS_RELU, true, true>(g);
-    else          mx_launch<MX_EPI_BIAS_RELU, true, false>(g);
+    if (out_fp32) mx_launch<Epi::BiasRelu, true, true>(g);
+    else          mx_launch<Epi::BiasRelu, true, false>(g);
   } else {
-    if (out_fp32) mx_launch<MX_EPI_BIAS_RELU, false, true>(g);
-    else          mx_launch<MX_EPI_BIAS_RELU, false, false>(g);
+    if (out_fp32) mx_launch<Epi::BiasRelu, false, true>(g);
+    else          mx_launch<Epi::BiasRelu, false, false>(g);
   }
   return C;
 }
@@ -956,15 +719,15 @@ at::Tensor gemm_mx8_relu_dot_hip(const at::Tensor& a8, int64_t ea,
   g.bias = mx_vec_n(op, "b2", b2, g.N);
   g.w3 = mx_vec_n(op, "w3", w3, g.N);
   TORCH_CHECK(g.bias && g.w3, op, ": b2 and w3 are required");
-  g.n_live = mx_n_live_ptr(n_dev, a8, op);
+  g.n_live = n_live_ptr(n_dev, a8, op);
   auto y = torch::zeros({g.M}, a8.options().dtype(torch::kFloat));
   if (g.empty()) return y;
   g.c = y.data_ptr();
   if (g.n_live)
-    mx_launch<MX_EPI_RELU_DOT, true, true, false, MX_FMT_E4M3, MX_FMT_E4M3,
+    mx_launch<Epi::ReluDot, true, true, false, MX_FMT_E4M3, MX_FMT_E4M3,
               false, true>(g);
   else
-    mx_launch<MX_EPI_RELU_DOT, true, true>(g);
+    mx_launch<Epi::ReluDot, true, true>(g);
   return y;
 }
 
@@ -985,8 +748,8 @@ std::tuple<at::Tensor, at::Tensor> gemm_mx8_relu_mask_hip(
   if (g.empty()) return {C, mask};
   g.c = C.data_ptr();
   g.mask_out = mask.data_ptr<unsigned char>();
-  if (g.bias) mx_launch<MX_EPI_BIAS_RELU, true, false, true>(g);
-  else        mx_launch<MX_EPI_BIAS_RELU, false, false, true>(g);
+  if (g.bias) mx_launch<Epi::BiasRelu, true, false, true>(g);
+  else        mx_launch<Epi::BiasRelu, false, false, true>(g);
   return {C, mask};
 }
 
@@ -1049,33 +812,24 @@ at::Tensor quantize_e5m2_hip(const at::Tensor& x, int64_t e,
 std::tuple<at::Tensor, at::Tensor> expand1d_bf16_e5m2_hip(
     const at::Tensor& x, const at::Tensor& w, const at::Tensor& mask,
     const at::Tensor& e_dev) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() &&
-                  x.scalar_type() == at::kFloat,
-              "expand1d_bf16_e5m2: x must be contiguous fp32 cuda");
-  TORCH_CHECK(w.is_cuda() && w.is_contiguous() &&
-                  w.scalar_type() == at::kBFloat16,
-              "expand1d_bf16_e5m2: w must be contiguous bf16 cuda");
-  const long long n = x.numel();
-  const long long H = w.numel();
-  TORCH_CHECK(H % 8 == 0, "expand1d_bf16_e5m2: H must be a multiple of 8");
+  const char* op = "expand1d_bf16_e5m2";
+  const Expand1dArgs a = expand1d_args(op, x, w, c10::nullopt);
+  TORCH_CHECK(x.is_contiguous() && w.is_cuda() && w.is_contiguous(), op,
+              ": x and w must be contiguous cuda tensors");
   TORCH_CHECK(mask.is_cuda() && mask.is_contiguous() &&
                   mask.scalar_type() == at::kByte &&
-                  mask.numel() == n * (H / 8),
-              "expand1d_bf16_e5m2: mask must be uint8 [n, H/8] bitmask");
-  const int* edp =
-      mx_edev_ptr(c10::optional<at::Tensor>(e_dev), x, "expand1d_bf16_e5m2");
-  TORCH_CHECK(edp != nullptr, "expand1d_bf16_e5m2: e_dev required");
-  auto out = at::empty({n, H}, w.options());
-  auto out8 = at::empty({n, H}, w.options().dtype(at::kByte));
-  long long total = n * (H / 8);
-  if (total == 0) return {out, out8};
+                  mask.numel() == a.n * a.h8,
+              op, ": mask must be uint8 [n, H/8] bitmask");
+  const int* edp = mx_edev_ptr(c10::optional<at::Tensor>(e_dev), x, op);
+  TORCH_CHECK(edp != nullptr, op, ": e_dev required");
+  auto out = at::empty({a.n, a.H}, w.options());
+  auto out8 = at::empty({a.n, a.H}, w.options().dtype(at::kByte));
+  if (a.grid == 0) return {out, out8};
   auto stream = at::cuda::getCurrentCUDAStream();
-  int grid = (int)std::min<long long>((total + 255) / 256, 2048);
-  hipLaunchKernelGGL(expand1d_bf16_e5m2_kernel, dim3(grid), dim3(256), 0,
-                     stream, x.data_ptr<float>(), (const bf16_t*)w.data_ptr(),
-                     mask.data_ptr<unsigned char>(), edp,
+  hipLaunchKernelGGL(expand1d_bf16_e5m2_kernel, dim3(a.grid), dim3(256), 0,
+                     stream, a.x, a.w, mask.data_ptr<unsigned char>(), edp,
                      (bf16_t*)out.data_ptr(), out8.data_ptr<unsigned char>(),
-                     n, (int)(H / 8));
+                     a.n, a.h8);
   return {out, out8};
 }
 
@@ -1101,7 +855,7 @@ at::Tensor transpose_u8_hip(const at::Tensor& src) {
 }
 
 // the four operand-format pairs of one (epilogue, output type)
-template <int EPI, bool OUT_FP32>
+template <Epi EPI, bool OUT_FP32>
 static void mx_launch_fmt(const MxGemm& g, int64_t a_fmt, int64_t b_fmt) {
   constexpr int E4 = MX_FMT_E4M3, E5 = MX_FMT_E5M2;
   if (a_fmt == E4) {
@@ -1148,11 +902,11 @@ at::Tensor gemm_mx8_nt_fmt_hip(const at::Tensor& a8, int64_t ea,
   if (g.empty()) return C;
   g.c = C.data_ptr();
   if (g.mask_in) {
-    if (out_fp32) mx_launch_fmt<MX_EPI_MASK_MUL, true>(g, a_fmt, b_fmt);
-    else          mx_launch_fmt<MX_EPI_MASK_MUL, false>(g, a_fmt, b_fmt);
+    if (out_fp32) mx_launch_fmt<Epi::MaskMul, true>(g, a_fmt, b_fmt);
+    else          mx_launch_fmt<Epi::MaskMul, false>(g, a_fmt, b_fmt);
   } else {
-    if (out_fp32) mx_launch_fmt<MX_EPI_NONE, true>(g, a_fmt, b_fmt);
-    else          mx_launch_fmt<MX_EPI_NONE, false>(g, a_fmt, b_fmt);
+    if (out_fp32) mx_launch_fmt<Epi::None, true>(g, a_fmt, b_fmt);
+    else          mx_launch_fmt<Epi::None, false>(g, a_fmt, b_fmt);
   }
   return C;
 }

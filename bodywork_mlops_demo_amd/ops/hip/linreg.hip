@@ -25,6 +25,8 @@
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 
+#include "host_checks.h"
+#include "live_rows.h"
 #include "philox.h"
 #include "reduce.h"
 
@@ -214,10 +216,7 @@ __global__ void linear_score_kernel(const float* __restrict__ x,
   // size n): a captured replay over a padded bucket then touches only the
   // rows that exist.
   const float a = ab[0], b = ab[1];
-  if (n_live != nullptr) {
-    long long live = (long long)*n_live;
-    n = live < 0 ? 0 : (live < n ? live : n);
-  }
+  if (n_live != nullptr) n = live_count(n_live, n);
   const long long stride = (long long)gridDim.x * blockDim.x;
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long n4 = n >> 2;
@@ -239,12 +238,7 @@ at::Tensor linear_score_hip(const at::Tensor& x, const at::Tensor& ab,
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat);
   TORCH_CHECK(ab.is_cuda() && ab.numel() == 2 &&
               ab.scalar_type() == at::kFloat);
-  const int64_t* n_live = nullptr;
-  if (n_dev.has_value()) {
-    TORCH_CHECK(n_dev->is_cuda() && n_dev->numel() == 1 &&
-                n_dev->scalar_type() == at::kLong);
-    n_live = n_dev->data_ptr<int64_t>();
-  }
+  const int64_t* n_live = n_live_ptr(n_dev, x, "linear_score");
   long long n = x.numel();
   auto out = at::empty_like(x);
   auto stream = at::cuda::getCurrentCUDAStream();

@@ -13,6 +13,9 @@
 #include <torch/extension.h>
 
 #include "bf16_utils.h"
+#include "expand1d.h"
+#include "host_checks.h"
+#include "live_rows.h"
 #include "reduce.h"
 
 // ---- expand1d -------------------------------------------------------------
@@ -36,9 +39,12 @@ __global__ void expand1d_kernel(const float* __restrict__ x,
                                 const int64_t* __restrict__ n_live = nullptr) {
   if constexpr (LIVE) {
     static_assert(RELU && !HAS_MASK && !EMIT_MASK, "live rows: scoring only");
-    long long live = (long long)*n_live;
-    n = live < 0 ? 0 : (live < n ? live : n);
+    n = live_count(n_live, n);
   }
+  // This kernel keeps its own loop: built from expand1d.h's pieces its plain
+  // variants measured 0.7-0.9% slower (profiles/shared_tile_epilogue.md).
+  // The arithmetic is e1d_axpb / e1d_apply_mask / e1d_mask_bits /
+  // e1d_store_bf16 written out; the tests compare the outputs bitwise.
   const long long total = (long long)n * h8;
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -74,63 +80,42 @@ std::tuple<at::Tensor, at::Tensor> expand1d_bf16_hip(
     const c10::optional<at::Tensor>& b, bool relu,
     const c10::optional<at::Tensor>& mask, bool emit_mask,
     const c10::optional<at::Tensor>& n_dev) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat);
-  TORCH_CHECK(w.scalar_type() == at::kBFloat16);
+  const Expand1dArgs a = expand1d_args("expand1d", x, w, b);
   // n_dev (optional int64[1] device tensor): compute only the first n_dev
   // rows and leave the rest of the output unwritten.  Scoring use only.
-  const int64_t* n_live = nullptr;
-  if (n_dev.has_value() && n_dev->defined()) {
-    TORCH_CHECK(n_dev->is_cuda() && n_dev->device() == x.device() &&
-                    n_dev->numel() == 1 && n_dev->scalar_type() == at::kLong,
-                "expand1d: n_dev must be an int64[1] tensor on x's device");
-    TORCH_CHECK(relu && !mask.has_value() && !emit_mask,
-                "expand1d: n_dev serves the plain relu scoring use only "
-                "(no mask, no emit_mask)");
-    n_live = n_dev->data_ptr<int64_t>();
-  }
-  const long long n = x.numel();
-  const long long H = w.numel();
-  TORCH_CHECK(H % 8 == 0, "expand1d: H must be a multiple of 8");
-  auto out = at::empty({n, H}, w.options());
-  const bool has_bias = b.has_value();
+  const int64_t* n_live = n_live_ptr(n_dev, x, "expand1d");
+  TORCH_CHECK(!n_live || (relu && !mask.has_value() && !emit_mask),
+              "expand1d: n_dev serves the plain relu scoring use only "
+              "(no mask, no emit_mask)");
+  const bool has_bias = a.b != nullptr;
   const bool has_mask = mask.has_value();
+  auto out = at::empty({a.n, a.H}, w.options());
   at::Tensor mask_out;
   if (emit_mask)
-    mask_out = at::empty({n, H / 8}, w.options().dtype(at::kByte));
+    mask_out = at::empty({a.n, a.H / 8}, w.options().dtype(at::kByte));
   else
     mask_out = at::empty({0}, w.options().dtype(at::kByte));
   if (has_mask)
     TORCH_CHECK(mask->scalar_type() == at::kByte &&
-                mask->numel() == n * (H / 8),
+                mask->numel() == a.n * a.h8,
                 "expand1d: mask must be uint8 [n, H/8] bitmask");
+  if (a.grid == 0) return {out, mask_out};
   auto stream = at::cuda::getCurrentCUDAStream();
-  long long total = n * (H / 8);
-  int grid = (int)std::min<long long>((total + 255) / 256, 2048);
-  const bf16_t* wp = (const bf16_t*)w.data_ptr();
-  const bf16_t* bp = has_bias ? (const bf16_t*)b->data_ptr() : nullptr;
   const unsigned char* mp =
       has_mask ? (const unsigned char*)mask->data_ptr() : nullptr;
   unsigned char* mop =
       emit_mask ? (unsigned char*)mask_out.data_ptr() : nullptr;
 
-#define LAUNCH_E1D(R, B_, M_, E_)                                         \
-  hipLaunchKernelGGL((expand1d_kernel<R, B_, M_, E_>), dim3(grid),        \
-                     dim3(256), 0, stream, x.data_ptr<float>(), wp, bp,   \
-                     mp, mop, (bf16_t*)out.data_ptr(), n, (int)(H / 8))
+#define LAUNCH_E1D(R, B_, M_, E_, ...)                                    \
+  hipLaunchKernelGGL((expand1d_kernel<R, B_, M_, E_, ##__VA_ARGS__>),     \
+                     dim3(a.grid), dim3(256), 0, stream, a.x, a.w, a.b,   \
+                     mp, mop, (bf16_t*)out.data_ptr(), a.n, a.h8, n_live)
 #define LAUNCH_E1D_E(R, B_, M_)                                           \
   do { if (emit_mask) LAUNCH_E1D(R, B_, M_, true);                        \
        else LAUNCH_E1D(R, B_, M_, false); } while (0)
   if (n_live) {
-    if (has_bias)
-      hipLaunchKernelGGL((expand1d_kernel<true, true, false, false, true>),
-                         dim3(grid), dim3(256), 0, stream,
-                         x.data_ptr<float>(), wp, bp, mp, mop,
-                         (bf16_t*)out.data_ptr(), n, (int)(H / 8), n_live);
-    else
-      hipLaunchKernelGGL((expand1d_kernel<true, false, false, false, true>),
-                         dim3(grid), dim3(256), 0, stream,
-                         x.data_ptr<float>(), wp, bp, mp, mop,
-                         (bf16_t*)out.data_ptr(), n, (int)(H / 8), n_live);
+    if (has_bias) LAUNCH_E1D(true, true, false, false, true);
+    else          LAUNCH_E1D(true, false, false, false, true);
   } else if (relu) {
     if (has_bias) { if (has_mask) LAUNCH_E1D_E(true, true, true); else LAUNCH_E1D_E(true, true, false); }
     else          { if (has_mask) LAUNCH_E1D_E(true, false, true); else LAUNCH_E1D_E(true, false, false); }
@@ -190,15 +175,17 @@ at::Tensor rowdot_bf16_hip(const at::Tensor& h, const at::Tensor& w,
   return out;
 }
 
-// ---- coldot (+ optional colsum) ------------------------------------------
+// ---- coldot / colsum -------------------------------------------------------
 // block covers 2048 consecutive columns (256 threads x 8); rows split
 // across gridDim.y chunks; one fp32 atomicAdd per output per chunk.
+// DOT: dw[j] = sum_i m[i,j]*v[i];  COLSUM: cs[j] = sum_i m[i,j].
 
-template <bool ALSO_COLSUM>
+template <bool DOT, bool COLSUM>
 __global__ void coldot_kernel(const bf16_t* __restrict__ m,
                               const float* __restrict__ v,
                               float* __restrict__ dw, float* __restrict__ cs,
                               long long n, int H) {
+  static_assert(DOT || COLSUM, "nothing to compute");
   const int col0 = (blockIdx.x * blockDim.x + threadIdx.x) * 8;
   if (col0 >= H) return;
   const long long rows_per_chunk = (n + gridDim.y - 1) / gridDim.y;
@@ -214,7 +201,7 @@ __global__ void coldot_kernel(const bf16_t* __restrict__ m,
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       raw[u] = load_bf16x8(m + (r + u) * (long long)H + col0);
-      vv[u] = v[r + u];
+      if (DOT) vv[u] = v[r + u];
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -222,101 +209,73 @@ __global__ void coldot_kernel(const bf16_t* __restrict__ m,
       bf16x8_to_f32(raw[u], mv);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        dot[e] = fmaf(mv[e], vv[u], dot[e]);
-        if (ALSO_COLSUM) sum[e] += mv[e];
+        if (DOT) dot[e] = fmaf(mv[e], vv[u], dot[e]);
+        if (COLSUM) sum[e] += mv[e];
       }
     }
   }
   for (; r < r1; ++r) {
-    float vv = v[r];
+    float vv = DOT ? v[r] : 0.0f;
     float mv[8];
     bf16x8_to_f32(load_bf16x8(m + r * (long long)H + col0), mv);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      dot[e] = fmaf(mv[e], vv, dot[e]);
-      if (ALSO_COLSUM) sum[e] += mv[e];
+      if (DOT) dot[e] = fmaf(mv[e], vv, dot[e]);
+      if (COLSUM) sum[e] += mv[e];
     }
   }
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
-    atomicAdd(&dw[col0 + e], dot[e]);
-    if (ALSO_COLSUM) atomicAdd(&cs[col0 + e], sum[e]);
+    if (DOT) atomicAdd(&dw[col0 + e], dot[e]);
+    if (COLSUM) atomicAdd(&cs[col0 + e], sum[e]);
   }
 }
 
-at::Tensor coldot_bf16_hip(const at::Tensor& m, const at::Tensor& v,
-                           bool also_colsum) {
-  TORCH_CHECK(m.is_cuda() && m.dim() == 2);
-  TORCH_CHECK(m.scalar_type() == at::kBFloat16 &&
-              v.scalar_type() == at::kFloat);
+// m must be a bf16 [n, H] cuda matrix with H % 8 == 0; returns the grid
+static dim3 coldot_grid(const char* op, const at::Tensor& m) {
+  TORCH_CHECK(m.is_cuda() && m.dim() == 2 &&
+                  m.scalar_type() == at::kBFloat16,
+              op, ": m must be a 2-d bf16 cuda tensor");
   const long long n = m.size(0);
   const int H = (int)m.size(1);
-  TORCH_CHECK(H % 8 == 0, "coldot: H must be a multiple of 8");
-  auto out = at::zeros({also_colsum ? 2 : 1, H},
-                       m.options().dtype(at::kFloat));
-  auto stream = at::cuda::getCurrentCUDAStream();
+  TORCH_CHECK(H % 8 == 0, op, ": H must be a multiple of 8");
   int gx = (H / 8 + 255) / 256;
   // >=4 waves/SIMD: 256 y-chunks gave only 1 workgroup/CU (4 waves) and
   // measured ~2-3.7 TB/s; 128-row chunks fill the chip (atomic fan-in
   // per column stays <=1024, negligible)
   int gy = (int)std::min<long long>((n + 127) / 128, 1024);
+  return dim3(gx, gy);
+}
+
+at::Tensor coldot_bf16_hip(const at::Tensor& m, const at::Tensor& v,
+                           bool also_colsum) {
+  const dim3 grid = coldot_grid("coldot", m);
+  TORCH_CHECK(v.scalar_type() == at::kFloat);
+  const long long n = m.size(0);
+  const int H = (int)m.size(1);
+  auto out = at::zeros({also_colsum ? 2 : 1, H},
+                       m.options().dtype(at::kFloat));
+  auto stream = at::cuda::getCurrentCUDAStream();
   float* dw = out.data_ptr<float>();
-  float* cs = also_colsum ? dw + H : nullptr;
   if (also_colsum)
-    hipLaunchKernelGGL((coldot_kernel<true>), dim3(gx, gy), dim3(256), 0,
+    hipLaunchKernelGGL((coldot_kernel<true, true>), grid, dim3(256), 0,
                        stream, (const bf16_t*)m.data_ptr(),
-                       v.data_ptr<float>(), dw, cs, n, H);
+                       v.data_ptr<float>(), dw, dw + H, n, H);
   else
-    hipLaunchKernelGGL((coldot_kernel<false>), dim3(gx, gy), dim3(256), 0,
+    hipLaunchKernelGGL((coldot_kernel<true, false>), grid, dim3(256), 0,
                        stream, (const bf16_t*)m.data_ptr(),
                        v.data_ptr<float>(), dw, nullptr, n, H);
   return out;
 }
 
-// colsum alone = coldot with v == 1 fused path
-__global__ void colsum_kernel(const bf16_t* __restrict__ m,
-                              float* __restrict__ cs, long long n, int H) {
-  const int col0 = (blockIdx.x * blockDim.x + threadIdx.x) * 8;
-  if (col0 >= H) return;
-  const long long rows_per_chunk = (n + gridDim.y - 1) / gridDim.y;
-  const long long r0 = blockIdx.y * rows_per_chunk;
-  const long long r1 = min(r0 + rows_per_chunk, n);
-  float sum[8] = {0};
-  long long r = r0;
-  for (; r + 3 < r1; r += 4) {
-    bf16x8 raw[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      raw[u] = load_bf16x8(m + (r + u) * (long long)H + col0);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      float mv[8];
-      bf16x8_to_f32(raw[u], mv);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) sum[e] += mv[e];
-    }
-  }
-  for (; r < r1; ++r) {
-    float mv[8];
-    bf16x8_to_f32(load_bf16x8(m + r * (long long)H + col0), mv);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) sum[e] += mv[e];
-  }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) atomicAdd(&cs[col0 + e], sum[e]);
-}
-
 at::Tensor colsum_bf16_hip(const at::Tensor& m) {
-  TORCH_CHECK(m.is_cuda() && m.dim() == 2 &&
-              m.scalar_type() == at::kBFloat16);
+  const dim3 grid = coldot_grid("colsum", m);
   const long long n = m.size(0);
   const int H = (int)m.size(1);
-  TORCH_CHECK(H % 8 == 0);
   auto out = at::zeros({H}, m.options().dtype(at::kFloat));
   auto stream = at::cuda::getCurrentCUDAStream();
-  int gx = (H / 8 + 255) / 256;
-  int gy = (int)std::min<long long>((n + 127) / 128, 1024);
-  hipLaunchKernelGGL(colsum_kernel, dim3(gx, gy), dim3(256), 0, stream,
-                     (const bf16_t*)m.data_ptr(), out.data_ptr<float>(), n, H);
+  hipLaunchKernelGGL((coldot_kernel<false, true>), grid, dim3(256), 0, stream,
+                     (const bf16_t*)m.data_ptr(), nullptr, nullptr,
+                     out.data_ptr<float>(), n, H);
   return out;
 }
