@@ -313,9 +313,7 @@ def regression_metrics(y: torch.Tensor, yhat: torch.Tensor) -> dict:
     (``mean_absolute_percentage_error``, ``r2_score``, ``max_error`` —
     stage_1:79-90): MAPE uses |y - yhat| / max(|y|, eps).
     """
-    if y.device.type == "cuda":
-        return metrics_from_sums(regression_metric_sums(y, yhat))
-    return metrics_from_sums(reference.metric_sums_cpu(y, yhat))
+    return metrics_from_sums(regression_metric_sums(y, yhat))
 
 
 def linear_split_metrics(
@@ -382,7 +380,10 @@ def random_split(
 def train_test_split_indices(
     n: int, test_size: float = 0.2, seed: int = 42, device: str | torch.device = "cpu"
 ) -> tuple[torch.Tensor, torch.Tensor]:
-    """Random permutation split (GPU permutation via philox keyed sort)."""
+    """Random permutation split: ``(train_idx, test_idx)`` from a seeded
+    ``torch.randperm`` drawn on the CPU, the first ``round(n * test_size)``
+    indices being the test rows; the index tensors are then moved to
+    ``device``.  Unrelated to the philox split of :func:`random_split`."""
     device = torch.device(device)
     g = torch.Generator(device="cpu").manual_seed(seed)
     perm = torch.randperm(n, generator=g)

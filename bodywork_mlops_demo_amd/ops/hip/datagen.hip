@@ -18,15 +18,61 @@
 #define DG_BLOCK 256
 #define DG_WAVES (DG_BLOCK / 64)
 
+// ---- stable compaction: the two per-block pieces --------------------------
+// Pass 1 counts each block's flagged threads, a scan of the counts gives
+// every block its offset, pass 2 adds a thread's position within its block.
+
+// How many threads of the block have `flag` set (valid in thread 0, 0
+// elsewhere): wave popcount -> LDS -> thread-0 add.
+__device__ __forceinline__ unsigned int block_flag_count(int flag) {
+  __shared__ unsigned int wave_cnt[DG_WAVES];
+  unsigned long long ballot = __ballot(flag);
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  if (lane == 0) wave_cnt[wave] = (unsigned int)__popcll(ballot);
+  __syncthreads();
+  unsigned int c = 0;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 0; w < DG_WAVES; ++w) c += wave_cnt[w];
+  }
+  return c;
+}
+
+// How many threads of the block ahead of this one have `flag` set: an
+// exclusive scan of the wave popcounts plus the flagged lanes below mine.
+__device__ __forceinline__ unsigned int block_flag_position(int flag) {
+  __shared__ unsigned int wave_off[DG_WAVES];
+  unsigned long long ballot = __ballot(flag);
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  if (lane == 0) wave_off[wave] = (unsigned int)__popcll(ballot);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned int acc = 0;
+#pragma unroll
+    for (int w = 0; w < DG_WAVES; ++w) {
+      unsigned int c = wave_off[w];
+      wave_off[w] = acc;
+      acc += c;
+    }
+  }
+  __syncthreads();
+  unsigned int before =
+      (unsigned int)__popcll(ballot & ((1ull << lane) - 1ull));
+  return wave_off[wave] + before;
+}
+
 __global__ void datagen_generate_kernel(
     float* __restrict__ y_tmp, float* __restrict__ X_tmp,
     unsigned int* __restrict__ block_counts, long long n,
-    unsigned long long stream_offset, unsigned int key0, unsigned int key1,
-    float alpha, float beta, float sigma) {
+    unsigned long long stream_offset, PhiloxKey key, float alpha, float beta,
+    float sigma) {
   const long long i = (long long)blockIdx.x * DG_BLOCK + threadIdx.x;
   int keep = 0;
   if (i < n) {
-    Philox4 r = philox4x32(stream_offset + (unsigned long long)i, key0, key1);
+    Philox4 r = philox4x32(stream_offset + (unsigned long long)i, key.key0,
+                           key.key1);
     float X = u32_to_uniform(r.x) * 100.0f;
     float u1 = ((float)r.y + 0.5f) * 2.3283064365386963e-10f;
     float u2 = u32_to_uniform(r.z);
@@ -36,19 +82,8 @@ __global__ void datagen_generate_kernel(
     y_tmp[i] = y;
     keep = y >= 0.0f;
   }
-  // per-block keep count: wave popcount -> LDS -> wave-0 add
-  __shared__ unsigned int wave_cnt[DG_WAVES];
-  unsigned long long ballot = __ballot(keep);
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  if (lane == 0) wave_cnt[wave] = (unsigned int)__popcll(ballot);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned int c = 0;
-#pragma unroll
-    for (int w = 0; w < DG_WAVES; ++w) c += wave_cnt[w];
-    block_counts[blockIdx.x] = c;
-  }
+  const unsigned int c = block_flag_count(keep);
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = c;
 }
 
 // ---- two-level exclusive scan over block counts ---------------------------
@@ -115,6 +150,32 @@ __global__ void scan_level2_kernel(unsigned int* __restrict__ out,
   }
 }
 
+// Exclusive scan of the per-block counts: {block offsets (uint32, one per
+// block), total (int32[1], on the device)}.  scan_level2 always writes the
+// total; int32 storage (count <= n < 2^31) so the host can read it back
+// without a dtype-conversion kernel.
+static std::pair<at::Tensor, at::Tensor> scan_block_counts(
+    const at::Tensor& counts, const char* op, hipStream_t stream) {
+  const long long n_blocks = counts.numel();
+  const long long n_chunks = (n_blocks + SCAN_CHUNK - 1) / SCAN_CHUNK;
+  TORCH_CHECK(n_chunks <= 4096, op,
+              ": n too large for the two-level scan (max ~1.07e9 rows per "
+              "call; shard across calls)");
+  auto offsets = at::empty_like(counts);
+  auto chunk_sums = at::empty({n_chunks}, counts.options());
+  auto total = at::empty({1}, counts.options().dtype(at::kInt));
+  hipLaunchKernelGGL(scan_level1_kernel, dim3(n_chunks), dim3(256), 0, stream,
+                     (const unsigned int*)counts.data_ptr(),
+                     (unsigned int*)offsets.data_ptr(),
+                     (unsigned int*)chunk_sums.data_ptr(), n_blocks);
+  hipLaunchKernelGGL(scan_level2_kernel,
+                     dim3(std::min<long long>(2048, n_chunks * 4)), dim3(256),
+                     0, stream, (unsigned int*)offsets.data_ptr(),
+                     (unsigned int*)chunk_sums.data_ptr(),
+                     (unsigned int*)total.data_ptr(), n_blocks, (int)n_chunks);
+  return {offsets, total};
+}
+
 __global__ void datagen_scatter_kernel(
     const float* __restrict__ y_tmp, const float* __restrict__ X_tmp,
     const unsigned int* __restrict__ block_offsets,
@@ -127,26 +188,9 @@ __global__ void datagen_scatter_kernel(
     X = X_tmp[i];
     keep = y >= 0.0f;
   }
-  __shared__ unsigned int wave_off[DG_WAVES];
-  unsigned long long ballot = __ballot(keep);
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  if (lane == 0) wave_off[wave] = (unsigned int)__popcll(ballot);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned int acc = 0;
-#pragma unroll
-    for (int w = 0; w < DG_WAVES; ++w) {
-      unsigned int c = wave_off[w];
-      wave_off[w] = acc;
-      acc += c;
-    }
-  }
-  __syncthreads();
+  const unsigned int kept_before = block_flag_position(keep);
   if (keep) {
-    unsigned int before =
-        (unsigned int)__popcll(ballot & ((1ull << lane) - 1ull));
-    unsigned int pos = block_offsets[blockIdx.x] + wave_off[wave] + before;
+    unsigned int pos = block_offsets[blockIdx.x] + kept_before;
     y_out[pos] = y;
     X_out[pos] = X;
   }
@@ -160,39 +204,15 @@ std::tuple<at::Tensor, at::Tensor> datagen_hip(
   auto y_tmp = at::empty({n}, opts);
   auto X_tmp = at::empty({n}, opts);
   const long long n_blocks = (n + DG_BLOCK - 1) / DG_BLOCK;
-  const long long n_chunks = (n_blocks + SCAN_CHUNK - 1) / SCAN_CHUNK;
-  TORCH_CHECK(n_chunks <= 4096,
-              "datagen: n too large for the two-level scan (max ~1.07e9 rows "
-              "per call; shard across calls)");
-  auto u32 = at::TensorOptions().dtype(at::kUInt32).device(at::kCUDA);
-  auto counts = at::empty({n_blocks}, u32);
-  auto offsets = at::empty({n_blocks}, u32);
-  auto chunk_sums = at::empty({std::max<long long>(n_chunks, 1)}, u32);
-  // scan_level2 always writes the total; int32 storage (count <= n < 2^31)
-  // so the host can read it back without a dtype-conversion kernel
-  auto total = at::empty({1}, opts.dtype(at::kInt));
-
-  unsigned int key0 = (unsigned int)(seed & 0xFFFFFFFFll);
-  unsigned int key1 = (seed > 0xFFFFFFFFll) ? (unsigned int)(seed >> 32)
-                                            : 0x1F123BB5u;
+  auto counts = at::empty({n_blocks}, opts.dtype(at::kUInt32));
   auto stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL(datagen_generate_kernel, dim3(n_blocks), dim3(DG_BLOCK),
                      0, stream,
                      y_tmp.data_ptr<float>(), X_tmp.data_ptr<float>(),
                      (unsigned int*)counts.data_ptr(), (long long)n,
-                     (unsigned long long)stream_offset, key0, key1,
+                     (unsigned long long)stream_offset, datagen_key(seed),
                      (float)alpha, (float)beta, (float)sigma);
-  hipLaunchKernelGGL(scan_level1_kernel, dim3(n_chunks), dim3(256), 0, stream,
-                     (const unsigned int*)counts.data_ptr(),
-                     (unsigned int*)offsets.data_ptr(),
-                     (unsigned int*)chunk_sums.data_ptr(), (long long)n_blocks);
-  hipLaunchKernelGGL(scan_level2_kernel,
-                     dim3(std::min<long long>(2048, n_chunks * 4)), dim3(256),
-                     0, stream,
-                     (unsigned int*)offsets.data_ptr(),
-                     (unsigned int*)chunk_sums.data_ptr(),
-                     (unsigned int*)total.data_ptr(), (long long)n_blocks,
-                     (int)n_chunks);
+  auto [offsets, total] = scan_block_counts(counts, "datagen", stream);
   auto y_out = at::empty({n}, opts);
   auto X_out = at::empty({n}, opts);
   hipLaunchKernelGGL(datagen_scatter_kernel, dim3(n_blocks), dim3(DG_BLOCK), 0,
@@ -207,32 +227,19 @@ std::tuple<at::Tensor, at::Tensor> datagen_hip(
 }
 
 // ---- random 80/20 split (replaces sklearn train_test_split, stage_1:98) ---
-// Element i is a TEST row iff philox(seed, i).x < tau; both partitions keep
-// row order (stable).  Single pass + the same two-level scan as datagen:
-// no host-side permutation, no gather indices — the reference's CPU
-// shuffle was 2/3 of the GPU cycle's train phase before this kernel.
+// Element i is a TEST row iff is_test_row(key, i) (philox.h); both
+// partitions keep row order (stable).  Single pass + the same two-level
+// scan as datagen: no host-side permutation, no gather indices — the
+// reference's CPU shuffle was 2/3 of the GPU cycle's train phase before
+// this kernel.
 
 __global__ void split_flag_kernel(unsigned int* __restrict__ block_counts,
-                                  long long n, unsigned int key0,
-                                  unsigned int key1, unsigned int tau) {
+                                  long long n, SplitKey key) {
   const long long i = (long long)blockIdx.x * DG_BLOCK + threadIdx.x;
   int is_test = 0;
-  if (i < n) {
-    Philox4 r = philox4x32((unsigned long long)i, key0, key1);
-    is_test = r.x < tau;
-  }
-  __shared__ unsigned int wave_cnt[DG_WAVES];
-  unsigned long long ballot = __ballot(is_test);
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  if (lane == 0) wave_cnt[wave] = (unsigned int)__popcll(ballot);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned int c = 0;
-#pragma unroll
-    for (int w = 0; w < DG_WAVES; ++w) c += wave_cnt[w];
-    block_counts[blockIdx.x] = c;
-  }
+  if (i < n) is_test = is_test_row(key, (unsigned long long)i);
+  const unsigned int c = block_flag_count(is_test);
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = c;
 }
 
 __global__ void split_scatter_kernel(
@@ -240,34 +247,13 @@ __global__ void split_scatter_kernel(
     const unsigned int* __restrict__ test_offsets,
     float* __restrict__ X_tr, float* __restrict__ y_tr,
     float* __restrict__ X_te, float* __restrict__ y_te, long long n,
-    unsigned int key0, unsigned int key1, unsigned int tau) {
+    SplitKey key) {
   const long long i = (long long)blockIdx.x * DG_BLOCK + threadIdx.x;
   int is_test = 0;
+  if (i < n) is_test = is_test_row(key, (unsigned long long)i);
+  const unsigned int block_tests_before = block_flag_position(is_test);
   if (i < n) {
-    Philox4 r = philox4x32((unsigned long long)i, key0, key1);
-    is_test = r.x < tau;
-  }
-  __shared__ unsigned int wave_off[DG_WAVES];
-  unsigned long long ballot = __ballot(is_test);
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  if (lane == 0) wave_off[wave] = (unsigned int)__popcll(ballot);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned int acc = 0;
-#pragma unroll
-    for (int w = 0; w < DG_WAVES; ++w) {
-      unsigned int c = wave_off[w];
-      wave_off[w] = acc;
-      acc += c;
-    }
-  }
-  __syncthreads();
-  if (i < n) {
-    unsigned int before =
-        (unsigned int)__popcll(ballot & ((1ull << lane) - 1ull));
-    unsigned int tests_before =
-        test_offsets[blockIdx.x] + wave_off[wave] + before;
+    unsigned int tests_before = test_offsets[blockIdx.x] + block_tests_before;
     if (is_test) {
       X_te[tests_before] = X[i];
       y_te[tests_before] = y[i];
@@ -287,33 +273,13 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> random_split_hip(
   long long n = X.numel();
   if (n == 0) return {X, y, X, y};
   const long long n_blocks = (n + DG_BLOCK - 1) / DG_BLOCK;
-  const long long n_chunks = (n_blocks + SCAN_CHUNK - 1) / SCAN_CHUNK;
-  TORCH_CHECK(n_chunks <= 4096, "random_split: n too large (max ~1.07e9)");
-  auto u32 = at::TensorOptions().dtype(at::kUInt32).device(X.device());
-  auto counts = at::empty({n_blocks}, u32);
-  auto offsets = at::empty({n_blocks}, u32);
-  auto chunk_sums = at::empty({std::max<long long>(n_chunks, 1)}, u32);
-  // written by scan_level2; int32 (count <= n < 2^31) reads back directly
-  auto total = at::empty({1}, X.options().dtype(at::kInt));
-  unsigned int key0 = (unsigned int)(seed & 0xFFFFFFFFll);
-  unsigned int key1 = (seed > 0xFFFFFFFFll) ? (unsigned int)(seed >> 32)
-                                            : 0x85EBCA6Bu;  // split stream
-  unsigned int tau = (unsigned int)(test_frac * 4294967296.0);
+  auto opts = X.options();
+  auto counts = at::empty({n_blocks}, opts.dtype(at::kUInt32));
+  const SplitKey key = split_key(seed, test_frac);
   auto stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL(split_flag_kernel, dim3(n_blocks), dim3(DG_BLOCK), 0,
-                     stream, (unsigned int*)counts.data_ptr(), n, key0, key1,
-                     tau);
-  hipLaunchKernelGGL(scan_level1_kernel, dim3(n_chunks), dim3(256), 0, stream,
-                     (const unsigned int*)counts.data_ptr(),
-                     (unsigned int*)offsets.data_ptr(),
-                     (unsigned int*)chunk_sums.data_ptr(), (long long)n_blocks);
-  hipLaunchKernelGGL(scan_level2_kernel,
-                     dim3(std::min<long long>(2048, n_chunks * 4)), dim3(256),
-                     0, stream, (unsigned int*)offsets.data_ptr(),
-                     (unsigned int*)chunk_sums.data_ptr(),
-                     (unsigned int*)total.data_ptr(), (long long)n_blocks,
-                     (int)n_chunks);
-  auto opts = X.options();
+                     stream, (unsigned int*)counts.data_ptr(), n, key);
+  auto [offsets, total] = scan_block_counts(counts, "random_split", stream);
   auto X_tr = at::empty({n}, opts);
   auto y_tr = at::empty({n}, opts);
   auto X_te = at::empty({n}, opts);
@@ -322,8 +288,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> random_split_hip(
                      stream, X.data_ptr<float>(), y.data_ptr<float>(),
                      (const unsigned int*)offsets.data_ptr(),
                      X_tr.data_ptr<float>(), y_tr.data_ptr<float>(),
-                     X_te.data_ptr<float>(), y_te.data_ptr<float>(), n, key0,
-                     key1, tau);
+                     X_te.data_ptr<float>(), y_te.data_ptr<float>(), n, key);
   int64_t n_test = total.item<int32_t>();
   int64_t n_train = n - n_test;
   return {X_tr.narrow(0, 0, n_train), y_tr.narrow(0, 0, n_train),

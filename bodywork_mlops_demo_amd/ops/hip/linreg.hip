@@ -20,7 +20,9 @@
 // addresses costs ~12 ns each on MI355X — 250 us for an 80 MB pass that
 // streams in 19 us — and makes the sums depend on arrival order; the
 // two-stage form is bitwise reproducible.)  Accumulation in fp64 so
-// 1B-row sums stay exact to ~2^-40.
+// 1B-row sums stay exact to ~2^-40.  Stage 1 of the streaming reductions
+// is one kernel (stream_reduce.h) instantiated over the statistic types
+// below; two_stage_reduce is the one host driver.
 #include <ATen/cuda/CUDAContext.h>
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
@@ -28,26 +30,21 @@
 #include "host_checks.h"
 #include "live_rows.h"
 #include "philox.h"
-#include "reduce.h"
+#include "stream_reduce.h"
 
-#define RED_BLOCK 256
-#define RED_WAVES (RED_BLOCK / 64)
 // Reduction grid cap: 4 blocks of 256 threads on each of the 256 CUs (16
 // waves per CU keeps a streaming fp64 pass at bandwidth), and the finalise
 // block then reads at most 1024 partials per statistic.
 #define RED_GRID_CAP 1024
-
 // elementwise (scoring) kernels: Guideline 11 cap
-static inline int stream_grid(long long n, int per_thread = 4) {
-  long long want = (n + (long long)RED_BLOCK * per_thread - 1) /
-                   ((long long)RED_BLOCK * per_thread);
-  return (int)std::max<long long>(std::min<long long>(want, 2048), 1);
-}
+#define STREAM_GRID_CAP 2048
 
-static inline int reduce_grid(long long n, int per_thread = 4) {
+// blocks of RED_BLOCK threads for n rows at per_thread rows per thread and
+// sweep, at most `cap` of them
+static inline int capped_grid(long long n, int cap, int per_thread = 4) {
   long long want = (n + (long long)RED_BLOCK * per_thread - 1) /
                    ((long long)RED_BLOCK * per_thread);
-  return (int)std::max<long long>(std::min<long long>(want, RED_GRID_CAP), 1);
+  return (int)std::max<long long>(std::min<long long>(want, cap), 1);
 }
 
 // ---- stage 2 of every reduction ------------------------------------------
@@ -74,133 +71,88 @@ __global__ void reduce_finalize_kernel(const double* __restrict__ ws,
   if (off == 1 && threadIdx.x == 0) out[0] = n;
 }
 
-static at::Tensor reduce_finalize(const at::Tensor& ws, int grid, int K,
-                                  unsigned int max_mask, int off, double n,
-                                  hipStream_t stream) {
+// Both stages of a reduction over n rows on `like`'s device: grid ->
+// workspace -> stage 1 -> finalise.  launch(grid, ws, stream) starts the
+// stage-1 kernel, which fills ws[grid, K].
+template <class Launch>
+static at::Tensor two_stage_reduce(const at::Tensor& like, long long n,
+                                   int per_thread, int K,
+                                   unsigned int max_mask, int off,
+                                   Launch launch) {
+  const int grid = capped_grid(n, RED_GRID_CAP, per_thread);
+  auto ws = at::empty({(long long)grid * K}, like.options().dtype(at::kDouble));
+  auto stream = at::cuda::getCurrentCUDAStream();
+  launch(grid, ws.data_ptr<double>(), stream);
   auto out = at::empty({off + K}, ws.options());
   hipLaunchKernelGGL(reduce_finalize_kernel, dim3(1), dim3(RED_BLOCK), 0,
                      stream, ws.data_ptr<double>(), out.data_ptr<double>(),
-                     grid, K, max_mask, off, n);
+                     grid, K, max_mask, off, (double)n);
   return out;
 }
 
-static inline void split_keys(int64_t seed, double test_frac,
-                              unsigned int* key0, unsigned int* key1,
-                              unsigned int* tau) {
-  // must stay identical to random_split_hip (datagen.hip): same row sets
-  *key0 = (unsigned int)(seed & 0xFFFFFFFFll);
-  *key1 = (seed > 0xFFFFFFFFll) ? (unsigned int)(seed >> 32) : 0x85EBCA6Bu;
-  *tau = (unsigned int)(test_frac * 4294967296.0);
+// stream_reduce2_kernel<Stat> over the fp32 tensors (a, b); the workspace
+// and result layout come from Stat
+template <class Stat>
+static at::Tensor stream_reduce2(const at::Tensor& a, const at::Tensor& b,
+                                 const Stat& s) {
+  using L = stat_layout<Stat>;
+  const long long n = a.numel();
+  return two_stage_reduce(
+      a, n, 4, L::K, L::MAX_MASK, L::OFF,
+      [&](int grid, double* ws, hipStream_t stream) {
+        hipLaunchKernelGGL((stream_reduce2_kernel<Stat>), dim3(grid),
+                           dim3(RED_BLOCK), 0, stream, a.data_ptr<float>(),
+                           b.data_ptr<float>(), ws, n, s);
+      });
 }
 
 // ---- linreg_stats ---------------------------------------------------------
 
-// SPLIT: row i is skipped when it is a TEST row of random_split
-// (philox(key, i).x < tau); ws then carries the train-row count as
-// statistic 0, so K = 5 instead of 4.
+// ws row = [n_train?, sum_x, sum_y, sum_xx, sum_xy] over rows (x, y).
+// SPLIT: a TEST row of random_split is skipped and the row starts with the
+// train-row count.
 template <bool SPLIT>
-__global__ void linreg_stats_kernel(const float* __restrict__ x,
-                                    const float* __restrict__ y,
-                                    double* __restrict__ ws, long long n,
-                                    unsigned int key0, unsigned int key1,
-                                    unsigned int tau) {
-  // 4 independent partial accumulators per statistic (one per float4
-  // lane) break the per-iteration fp64 dependency chains that left the
-  // serial version at ~12% of HBM bandwidth
-  double sx[4] = {0, 0, 0, 0}, sy[4] = {0, 0, 0, 0};
-  double sxx[4] = {0, 0, 0, 0}, sxy[4] = {0, 0, 0, 0};
-  unsigned int cnt = 0;  // per-thread rows < 2^32
-  const long long stride = (long long)gridDim.x * RED_BLOCK;
-  long long i = (long long)blockIdx.x * RED_BLOCK + threadIdx.x;
-  const long long n4 = n & ~3ll;
-  for (long long j = i * 4; j < n4; j += stride * 4) {
-    float4 xv = *(const float4*)(x + j);
-    float4 yv = *(const float4*)(y + j);
-    const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
-    const float ys[4] = {yv.x, yv.y, yv.z, yv.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      double xd = xs[e], yd = ys[e];
-      if (SPLIT) {
-        // a dropped row contributes exact zeros to every sum
-        const bool train =
-            philox4x32((unsigned long long)(j + e), key0, key1).x >= tau;
-        xd = train ? xd : 0.0;
-        yd = train ? yd : 0.0;
-        cnt += train;
-      }
-      sx[e] += xd;
-      sy[e] += yd;
-      sxx[e] = fma(xd, xd, sxx[e]);
-      sxy[e] = fma(xd, yd, sxy[e]);
-    }
-  }
-  for (long long j = n4 + i; j < n; j += stride) {
-    double xv = x[j], yv = y[j];
+struct LinregSums {
+  static constexpr int NSUM = 4;
+  static constexpr int MAX_POS = -1;
+  static constexpr bool COUNTS = SPLIT;
+  SplitKey key;
+
+  __device__ void begin() {}
+  __device__ __forceinline__ void row(long long i, float x, float y,
+                                      double (&sum)[NSUM], double&,
+                                      unsigned int& cnt) const {
+    double xd = x, yd = y;
     if (SPLIT) {
-      const bool train =
-          philox4x32((unsigned long long)j, key0, key1).x >= tau;
-      xv = train ? xv : 0.0;
-      yv = train ? yv : 0.0;
+      // a dropped row contributes exact zeros to every sum
+      const bool train = !is_test_row(key, (unsigned long long)i);
+      xd = train ? xd : 0.0;
+      yd = train ? yd : 0.0;
       cnt += train;
     }
-    sx[0] += xv; sy[0] += yv;
-    sxx[0] = fma(xv, xv, sxx[0]);
-    sxy[0] = fma(xv, yv, sxy[0]);
+    sum[0] += xd;
+    sum[1] += yd;
+    sum[2] = fma(xd, xd, sum[2]);
+    sum[3] = fma(xd, yd, sum[3]);
   }
-#pragma unroll
-  for (int e = 1; e < 4; ++e) {
-    sx[0] += sx[e]; sy[0] += sy[e]; sxx[0] += sxx[e]; sxy[0] += sxy[e];
-  }
-  constexpr int K = SPLIT ? 5 : 4;
-  double* row = ws + (long long)blockIdx.x * K;
-  __shared__ double lds[RED_WAVES];
-  double t;
-  if (SPLIT) {
-    t = block_sum_f64<RED_WAVES>((double)cnt, lds);
-    if (threadIdx.x == 0) *row++ = t;
-  }
-  t = block_sum_f64<RED_WAVES>(sx[0], lds);
-  if (threadIdx.x == 0) row[0] = t;
-  t = block_sum_f64<RED_WAVES>(sy[0], lds);
-  if (threadIdx.x == 0) row[1] = t;
-  t = block_sum_f64<RED_WAVES>(sxx[0], lds);
-  if (threadIdx.x == 0) row[2] = t;
-  t = block_sum_f64<RED_WAVES>(sxy[0], lds);
-  if (threadIdx.x == 0) row[3] = t;
+};
+
+static void check_xy(const at::Tensor& x, const at::Tensor& y) {
+  TORCH_CHECK(x.is_cuda() && y.is_cuda() && x.numel() == y.numel());
+  TORCH_CHECK(x.scalar_type() == at::kFloat && y.scalar_type() == at::kFloat);
 }
 
 at::Tensor linreg_stats_hip(const at::Tensor& x, const at::Tensor& y) {
-  TORCH_CHECK(x.is_cuda() && y.is_cuda() && x.numel() == y.numel());
-  TORCH_CHECK(x.scalar_type() == at::kFloat && y.scalar_type() == at::kFloat);
-  long long n = x.numel();
-  const int grid = reduce_grid(n);
-  auto ws = at::empty({(long long)grid * 4}, x.options().dtype(at::kDouble));
-  auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL((linreg_stats_kernel<false>), dim3(grid),
-                     dim3(RED_BLOCK), 0, stream, x.data_ptr<float>(),
-                     y.data_ptr<float>(), ws.data_ptr<double>(), n, 0u, 0u,
-                     0u);
-  return reduce_finalize(ws, grid, 4, 0u, 1, (double)n, stream);
+  check_xy(x, y);
+  return stream_reduce2(x, y, LinregSums<false>{});
 }
 
 // [n_train, sum_x, sum_y, sum_xx, sum_xy] over the TRAIN rows of
 // random_split(x, y, test_frac, seed), without materialising the split.
 at::Tensor linreg_split_stats_hip(const at::Tensor& x, const at::Tensor& y,
                                   double test_frac, int64_t seed) {
-  TORCH_CHECK(x.is_cuda() && y.is_cuda() && x.numel() == y.numel());
-  TORCH_CHECK(x.scalar_type() == at::kFloat && y.scalar_type() == at::kFloat);
-  long long n = x.numel();
-  unsigned int key0, key1, tau;
-  split_keys(seed, test_frac, &key0, &key1, &tau);
-  const int grid = reduce_grid(n);
-  auto ws = at::empty({(long long)grid * 5}, x.options().dtype(at::kDouble));
-  auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL((linreg_stats_kernel<true>), dim3(grid),
-                     dim3(RED_BLOCK), 0, stream, x.data_ptr<float>(),
-                     y.data_ptr<float>(), ws.data_ptr<double>(), n, key0,
-                     key1, tau);
-  return reduce_finalize(ws, grid, 5, 0u, 0, 0.0, stream);
+  check_xy(x, y);
+  return stream_reduce2(x, y, LinregSums<true>{split_key(seed, test_frac)});
 }
 
 // ---- linear_score ---------------------------------------------------------
@@ -242,7 +194,7 @@ at::Tensor linear_score_hip(const at::Tensor& x, const at::Tensor& ab,
   long long n = x.numel();
   auto out = at::empty_like(x);
   auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(linear_score_kernel, dim3(stream_grid(n)),
+  hipLaunchKernelGGL(linear_score_kernel, dim3(capped_grid(n, STREAM_GRID_CAP)),
                      dim3(RED_BLOCK), 0, stream, x.data_ptr<float>(),
                      out.data_ptr<float>(), ab.data_ptr<float>(), n, n_live);
   return out;
@@ -262,6 +214,9 @@ at::Tensor linear_score_hip(const at::Tensor& x, const at::Tensor& ab,
 //   out[T+1 .. T+NF]          = X^T y
 // Host side solves the (ridge-regularised) normal equations.
 
+// Keeps a loop of its own (one row per thread, no float4, NF-dependent
+// accumulator count); shares the per-block reduce-and-store and the host
+// driver with the streaming reductions.
 template <int NF>
 __global__ void poly_stats_kernel(const float* __restrict__ x,
                                   const float* __restrict__ y,
@@ -291,39 +246,34 @@ __global__ void poly_stats_kernel(const float* __restrict__ x,
   }
   __shared__ double lds[RED_WAVES];
 #pragma unroll
-  for (int i = 0; i < TRI + NF; ++i) {
-    double v = block_sum_f64<RED_WAVES>(acc[i], lds);
-    if (threadIdx.x == 0) ws[(long long)blockIdx.x * (TRI + NF) + i] = v;
-  }
+  for (int i = 0; i < TRI + NF; ++i)
+    block_reduce_store<false>(
+        acc[i], lds, ws, (long long)blockIdx.x * (TRI + NF) + i);
 }
 
 at::Tensor poly_stats_hip(const at::Tensor& x, const at::Tensor& y,
                           int64_t nf, double mu, double s) {
-  TORCH_CHECK(x.is_cuda() && y.is_cuda() && x.numel() == y.numel());
-  TORCH_CHECK(x.scalar_type() == at::kFloat && y.scalar_type() == at::kFloat);
+  check_xy(x, y);
   TORCH_CHECK(nf >= 2 && nf <= 6, "poly_stats: 2 <= degree+1 <= 6");
-  long long n = x.numel();
-  int tri = (int)(nf * (nf + 1) / 2);
-  const int K = tri + (int)nf;
+  const long long n = x.numel();
+  const int K = (int)(nf * (nf + 1) / 2 + nf);
+  const float inv_s = (float)(1.0 / s);
   // one row per thread and sweep here, so 1 per_thread
-  const int nblk = reduce_grid(n, 1);
-  auto ws = at::empty({(long long)nblk * K}, x.options().dtype(at::kDouble));
-  auto stream = at::cuda::getCurrentCUDAStream();
-  dim3 grid(nblk);
-  float inv_s = (float)(1.0 / s);
-#define PS_LAUNCH(NF_)                                                     \
-  hipLaunchKernelGGL((poly_stats_kernel<NF_>), grid, dim3(RED_BLOCK), 0,   \
-                     stream, x.data_ptr<float>(), y.data_ptr<float>(),     \
-                     ws.data_ptr<double>(), n, (float)mu, inv_s)
-  switch (nf) {
-    case 2: PS_LAUNCH(2); break;
-    case 3: PS_LAUNCH(3); break;
-    case 4: PS_LAUNCH(4); break;
-    case 5: PS_LAUNCH(5); break;
-    default: PS_LAUNCH(6); break;
-  }
+  return two_stage_reduce(
+      x, n, 1, K, 0u, 1, [&](int grid, double* ws, hipStream_t stream) {
+#define PS_LAUNCH(NF_)                                                      \
+  hipLaunchKernelGGL((poly_stats_kernel<NF_>), dim3(grid), dim3(RED_BLOCK), \
+                     0, stream, x.data_ptr<float>(), y.data_ptr<float>(),   \
+                     ws, n, (float)mu, inv_s)
+        switch (nf) {
+          case 2: PS_LAUNCH(2); break;
+          case 3: PS_LAUNCH(3); break;
+          case 4: PS_LAUNCH(4); break;
+          case 5: PS_LAUNCH(5); break;
+          default: PS_LAUNCH(6); break;
+        }
 #undef PS_LAUNCH
-  return reduce_finalize(ws, nblk, K, 0u, 1, (double)n, stream);
+      });
 }
 
 // Horner-scheme polynomial scoring in the normalised basis; coefficients
@@ -350,7 +300,7 @@ at::Tensor poly_score_hip(const at::Tensor& x, const at::Tensor& coef,
   long long n = x.numel();
   auto out = at::empty_like(x);
   auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(poly_score_kernel, dim3(stream_grid(n)),
+  hipLaunchKernelGGL(poly_score_kernel, dim3(capped_grid(n, STREAM_GRID_CAP)),
                      dim3(RED_BLOCK), 0, stream, x.data_ptr<float>(),
                      out.data_ptr<float>(), coef.data_ptr<float>(),
                      (int)coef.numel(), (float)mu, (float)(1.0 / s), n);
@@ -360,111 +310,51 @@ at::Tensor poly_score_hip(const at::Tensor& x, const at::Tensor& coef,
 // ---- regression_metrics (offline: stage_1:79-90 semantics) ---------------
 // out = [n, sum_ape, ss_res, sum_y, sum_yy, max_resid]
 //
-// SPLIT: `x` holds the feature, yhat = fmaf(b, x, a) is computed in fp32
-// exactly as linear_score_kernel does, and only the TEST rows of
-// random_split count (philox(key, i).x < tau); ws then carries the
-// test-row count as statistic 0, so K = 6 instead of 5.
-
+// ws row = [n_test?, sum_ape, ss_res, sum_y, sum_yy, max_resid] over rows
+// (y, p).  Plain: p is the prediction.  SPLIT: p is the feature x, yhat =
+// fmaf(b, x, a) is computed in fp32 exactly as linear_score_kernel does,
+// only the TEST rows of random_split count, and the row starts with their
+// count.
 template <bool SPLIT>
-__global__ void regression_metrics_kernel(const float* __restrict__ y,
-                                          const float* __restrict__ x,
-                                          const float* __restrict__ ab,
-                                          double* __restrict__ ws,
-                                          long long n, unsigned int key0,
-                                          unsigned int key1,
-                                          unsigned int tau) {
-  const double MAPE_EPS = 2.220446049250313e-16;  // sklearn epsilon
-  double s_ape[4] = {0, 0, 0, 0}, ss_res[4] = {0, 0, 0, 0};
-  double s_y[4] = {0, 0, 0, 0}, s_yy[4] = {0, 0, 0, 0};
-  double max_res = 0;
-  unsigned int cnt = 0;
-  float a = 0.f, b = 0.f;
-  if (SPLIT) { a = ab[0]; b = ab[1]; }
-  const long long stride = (long long)gridDim.x * RED_BLOCK;
-  const long long i = (long long)blockIdx.x * RED_BLOCK + threadIdx.x;
-  const long long n4 = n & ~3ll;
-  for (long long j = i * 4; j < n4; j += stride * 4) {
-    float4 yv4 = *(const float4*)(y + j);
-    float4 pv4 = *(const float4*)(x + j);
-    const float ys[4] = {yv4.x, yv4.y, yv4.z, yv4.w};
-    const float ps[4] = {pv4.x, pv4.y, pv4.z, pv4.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float yf = ys[e], pf = ps[e];
-      if (SPLIT) {
-        // a non-test row becomes (y, yhat) = (0, 0): zero in every sum
-        // and in the max
-        const bool test =
-            philox4x32((unsigned long long)(j + e), key0, key1).x < tau;
-        pf = test ? fmaf(b, pf, a) : 0.f;
-        yf = test ? yf : 0.f;
-        cnt += test;
-      }
-      double yv = yf, r = (double)yf - pf;
-      double ar = fabs(r);
-      s_ape[e] += ar / fmax(fabs(yv), MAPE_EPS);
-      ss_res[e] = fma(r, r, ss_res[e]);
-      s_y[e] += yv;
-      s_yy[e] = fma(yv, yv, s_yy[e]);
-      max_res = fmax(max_res, ar);
-    }
+struct RegressionSums {
+  static constexpr int NSUM = 4;
+  static constexpr int MAX_POS = 4;
+  static constexpr bool COUNTS = SPLIT;
+  const float* ab;  // SPLIT: device [intercept, coef]
+  SplitKey key;
+  float a, b;
+
+  __device__ void begin() {
+    if (SPLIT) { a = ab[0]; b = ab[1]; }
   }
-  for (long long j = n4 + i; j < n; j += stride) {
-    float yf = y[j], pf = x[j];
+  __device__ __forceinline__ void row(long long i, float yf, float pf,
+                                      double (&sum)[NSUM], double& mx,
+                                      unsigned int& cnt) const {
+    const double MAPE_EPS = 2.220446049250313e-16;  // sklearn epsilon
     if (SPLIT) {
-      const bool test =
-          philox4x32((unsigned long long)j, key0, key1).x < tau;
+      // a non-test row becomes (y, yhat) = (0, 0): zero in every sum and
+      // in the max
+      const bool test = is_test_row(key, (unsigned long long)i);
       pf = test ? fmaf(b, pf, a) : 0.f;
       yf = test ? yf : 0.f;
       cnt += test;
     }
     double yv = yf, r = yv - pf;
     double ar = fabs(r);
-    s_ape[0] += ar / fmax(fabs(yv), MAPE_EPS);
-    ss_res[0] = fma(r, r, ss_res[0]);
-    s_y[0] += yv;
-    s_yy[0] = fma(yv, yv, s_yy[0]);
-    max_res = fmax(max_res, ar);
+    sum[0] += ar / fmax(fabs(yv), MAPE_EPS);
+    sum[1] = fma(r, r, sum[1]);
+    sum[2] += yv;
+    sum[3] = fma(yv, yv, sum[3]);
+    mx = fmax(mx, ar);
   }
-#pragma unroll
-  for (int e = 1; e < 4; ++e) {
-    s_ape[0] += s_ape[e]; ss_res[0] += ss_res[e];
-    s_y[0] += s_y[e]; s_yy[0] += s_yy[e];
-  }
-  constexpr int K = SPLIT ? 6 : 5;
-  double* row = ws + (long long)blockIdx.x * K;
-  __shared__ double lds[RED_WAVES];
-  double t;
-  if (SPLIT) {
-    t = block_sum_f64<RED_WAVES>((double)cnt, lds);
-    if (threadIdx.x == 0) *row++ = t;
-  }
-  t = block_sum_f64<RED_WAVES>(s_ape[0], lds);
-  if (threadIdx.x == 0) row[0] = t;
-  t = block_sum_f64<RED_WAVES>(ss_res[0], lds);
-  if (threadIdx.x == 0) row[1] = t;
-  t = block_sum_f64<RED_WAVES>(s_y[0], lds);
-  if (threadIdx.x == 0) row[2] = t;
-  t = block_sum_f64<RED_WAVES>(s_yy[0], lds);
-  if (threadIdx.x == 0) row[3] = t;
-  t = block_max_f64<RED_WAVES>(max_res, lds);
-  if (threadIdx.x == 0) row[4] = t;
-}
+};
 
 at::Tensor regression_metrics_hip(const at::Tensor& y,
                                   const at::Tensor& yhat) {
   TORCH_CHECK(y.is_cuda() && yhat.is_cuda() && y.numel() == yhat.numel());
-  long long n = y.numel();
   auto yf = y.scalar_type() == at::kFloat ? y : y.to(at::kFloat);
   auto pf = yhat.scalar_type() == at::kFloat ? yhat : yhat.to(at::kFloat);
-  const int grid = reduce_grid(n);
-  auto ws = at::empty({(long long)grid * 5}, y.options().dtype(at::kDouble));
-  auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL((regression_metrics_kernel<false>), dim3(grid),
-                     dim3(RED_BLOCK), 0, stream, yf.data_ptr<float>(),
-                     pf.data_ptr<float>(), (const float*)nullptr,
-                     ws.data_ptr<double>(), n, 0u, 0u, 0u);
-  return reduce_finalize(ws, grid, 5, 1u << 4, 1, (double)n, stream);
+  return stream_reduce2(yf, pf, RegressionSums<false>{});
 }
 
 // [n_test, sum_ape, ss_res, sum_y, sum_yy, max_resid] of the linear model
@@ -473,100 +363,43 @@ at::Tensor regression_metrics_hip(const at::Tensor& y,
 at::Tensor linear_split_metrics_hip(const at::Tensor& x, const at::Tensor& y,
                                     const at::Tensor& ab, double test_frac,
                                     int64_t seed) {
-  TORCH_CHECK(x.is_cuda() && y.is_cuda() && x.numel() == y.numel());
-  TORCH_CHECK(x.scalar_type() == at::kFloat && y.scalar_type() == at::kFloat);
+  check_xy(x, y);
   TORCH_CHECK(ab.is_cuda() && ab.numel() == 2 &&
               ab.scalar_type() == at::kFloat);
-  long long n = x.numel();
-  unsigned int key0, key1, tau;
-  split_keys(seed, test_frac, &key0, &key1, &tau);
-  const int grid = reduce_grid(n);
-  auto ws = at::empty({(long long)grid * 6}, x.options().dtype(at::kDouble));
-  auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL((regression_metrics_kernel<true>), dim3(grid),
-                     dim3(RED_BLOCK), 0, stream, y.data_ptr<float>(),
-                     x.data_ptr<float>(), ab.data_ptr<float>(),
-                     ws.data_ptr<double>(), n, key0, key1, tau);
-  return reduce_finalize(ws, grid, 6, 1u << 5, 0, 0.0, stream);
+  return stream_reduce2(
+      y, x,
+      RegressionSums<true>{ab.data_ptr<float>(), split_key(seed, test_frac)});
 }
 
 // ---- score_label_metrics (online: stage_4:87-113 semantics) ---------------
 // out = [n, sum_ape, max_ape, s_s, s_l, s_ss, s_ll, s_sl]
+//
+// ws row = [sum_ape, max_ape, s_s, s_l, s_ss, s_ll, s_sl] over rows
+// (score, label) = out[1..7]
+struct ScoreLabelSums {
+  static constexpr int NSUM = 6;
+  static constexpr int MAX_POS = 1;
+  static constexpr bool COUNTS = false;
 
-__global__ void score_label_metrics_kernel(const float* __restrict__ s,
-                                           const float* __restrict__ l,
-                                           double* __restrict__ ws,
-                                           long long n) {
-  double s_ape[4] = {0, 0, 0, 0}, s_s[4] = {0, 0, 0, 0};
-  double s_l[4] = {0, 0, 0, 0}, s_ss[4] = {0, 0, 0, 0};
-  double s_ll[4] = {0, 0, 0, 0}, s_sl[4] = {0, 0, 0, 0};
-  double max_ape = 0;
-  const long long stride = (long long)gridDim.x * RED_BLOCK;
-  const long long i = (long long)blockIdx.x * RED_BLOCK + threadIdx.x;
-  const long long n4 = n & ~3ll;
-  for (long long j = i * 4; j < n4; j += stride * 4) {
-    float4 sv4 = *(const float4*)(s + j);
-    float4 lv4 = *(const float4*)(l + j);
-    const float ss4[4] = {sv4.x, sv4.y, sv4.z, sv4.w};
-    const float ll4[4] = {lv4.x, lv4.y, lv4.z, lv4.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      double sv = ss4[e], lv = ll4[e];
-      double ape = fabs(sv / lv - 1.0);  // reference has no eps guard
-      s_ape[e] += ape;
-      max_ape = fmax(max_ape, ape);
-      s_s[e] += sv;
-      s_l[e] += lv;
-      s_ss[e] = fma(sv, sv, s_ss[e]);
-      s_ll[e] = fma(lv, lv, s_ll[e]);
-      s_sl[e] = fma(sv, lv, s_sl[e]);
-    }
+  __device__ void begin() {}
+  __device__ __forceinline__ void row(long long, float s, float l,
+                                      double (&sum)[NSUM], double& mx,
+                                      unsigned int&) const {
+    double sv = s, lv = l;
+    double ape = fabs(sv / lv - 1.0);  // reference has no eps guard
+    sum[0] += ape;
+    mx = fmax(mx, ape);
+    sum[1] += sv;
+    sum[2] += lv;
+    sum[3] = fma(sv, sv, sum[3]);
+    sum[4] = fma(lv, lv, sum[4]);
+    sum[5] = fma(sv, lv, sum[5]);
   }
-  for (long long j = n4 + i; j < n; j += stride) {
-    double sv = s[j], lv = l[j];
-    double ape = fabs(sv / lv - 1.0);
-    s_ape[0] += ape;
-    max_ape = fmax(max_ape, ape);
-    s_s[0] += sv; s_l[0] += lv;
-    s_ss[0] = fma(sv, sv, s_ss[0]);
-    s_ll[0] = fma(lv, lv, s_ll[0]);
-    s_sl[0] = fma(sv, lv, s_sl[0]);
-  }
-#pragma unroll
-  for (int e = 1; e < 4; ++e) {
-    s_ape[0] += s_ape[e]; s_s[0] += s_s[e]; s_l[0] += s_l[e];
-    s_ss[0] += s_ss[e]; s_ll[0] += s_ll[e]; s_sl[0] += s_sl[e];
-  }
-  double* row = ws + (long long)blockIdx.x * 7;
-  __shared__ double lds[RED_WAVES];
-  double t;
-  // ws row = [sum_ape, max_ape, s_s, s_l, s_ss, s_ll, s_sl] (out[1..7])
-  t = block_sum_f64<RED_WAVES>(s_ape[0], lds);
-  if (threadIdx.x == 0) row[0] = t;
-  t = block_max_f64<RED_WAVES>(max_ape, lds);
-  if (threadIdx.x == 0) row[1] = t;
-  t = block_sum_f64<RED_WAVES>(s_s[0], lds);
-  if (threadIdx.x == 0) row[2] = t;
-  t = block_sum_f64<RED_WAVES>(s_l[0], lds);
-  if (threadIdx.x == 0) row[3] = t;
-  t = block_sum_f64<RED_WAVES>(s_ss[0], lds);
-  if (threadIdx.x == 0) row[4] = t;
-  t = block_sum_f64<RED_WAVES>(s_ll[0], lds);
-  if (threadIdx.x == 0) row[5] = t;
-  t = block_sum_f64<RED_WAVES>(s_sl[0], lds);
-  if (threadIdx.x == 0) row[6] = t;
-}
+};
 
 at::Tensor score_label_metrics_hip(const at::Tensor& s, const at::Tensor& l) {
   TORCH_CHECK(s.is_cuda() && l.is_cuda() && s.numel() == l.numel());
-  long long n = s.numel();
   auto sf = s.scalar_type() == at::kFloat ? s : s.to(at::kFloat);
   auto lf = l.scalar_type() == at::kFloat ? l : l.to(at::kFloat);
-  const int grid = reduce_grid(n);
-  auto ws = at::empty({(long long)grid * 7}, s.options().dtype(at::kDouble));
-  auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(score_label_metrics_kernel, dim3(grid),
-                     dim3(RED_BLOCK), 0, stream, sf.data_ptr<float>(),
-                     lf.data_ptr<float>(), ws.data_ptr<double>(), n);
-  return reduce_finalize(ws, grid, 7, 1u << 1, 1, (double)n, stream);
+  return stream_reduce2(sf, lf, ScoreLabelSums{});
 }

@@ -7,6 +7,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
+
 #define PHILOX_M0 0xD2511F53u
 #define PHILOX_M1 0xCD9E8D57u
 #define PHILOX_W0 0x9E3779B9u
@@ -38,6 +40,45 @@ __device__ __forceinline__ Philox4 philox4x32(unsigned long long counter,
     k1 += PHILOX_W1;
   }
   return {c0, c1, c2, c3};
+}
+
+// ---- the project's two philox streams, side by side -----------------------
+// key = (lo32(seed), hi32(seed)); a seed that fits 32 bits takes the
+// stream's own default second key word instead, so the data generator and
+// the train/test split never draw from the same stream for one seed
+// (ops/reference.py: datagen_cpu / _SPLIT_KEY1).
+#define PHILOX_DATAGEN_KEY1 0x1F123BB5u
+#define PHILOX_SPLIT_KEY1 0x85EBCA6Bu
+
+struct PhiloxKey {
+  unsigned int key0, key1;
+};
+
+static inline PhiloxKey philox_key(int64_t seed, unsigned int default_key1) {
+  return {(unsigned int)(seed & 0xFFFFFFFFll),
+          (seed > 0xFFFFFFFFll) ? (unsigned int)(seed >> 32) : default_key1};
+}
+
+static inline PhiloxKey datagen_key(int64_t seed) {
+  return philox_key(seed, PHILOX_DATAGEN_KEY1);
+}
+
+// The train/test split: row i is a TEST row iff philox(key, i).x < tau,
+// tau = test_frac * 2^32.  random_split and the fused linear fit
+// (linreg_split_stats / linear_split_metrics) all ask is_test_row, so they
+// see the same row sets by construction.
+struct SplitKey {
+  unsigned int key0, key1, tau;
+};
+
+static inline SplitKey split_key(int64_t seed, double test_frac) {
+  const PhiloxKey k = philox_key(seed, PHILOX_SPLIT_KEY1);
+  return {k.key0, k.key1, (unsigned int)(test_frac * 4294967296.0)};
+}
+
+__device__ __forceinline__ bool is_test_row(const SplitKey& k,
+                                            unsigned long long i) {
+  return philox4x32(i, k.key0, k.key1).x < k.tau;
 }
 
 // uniform in [0,1): u32 * 2^-32 (matches the numpy oracle's float32 math)

@@ -67,9 +67,12 @@ class TestDatagenGPU:
         y = X * 2
         Xtr, ytr, Xte, yte = ops.random_split(X, y, 0.2, seed=3)
         assert Xtr.shape[0] + Xte.shape[0] == X.shape[0]
-        Xtr_c, _, Xte_c, _ = ops.random_split(X.cpu(), y.cpu(), 0.2, seed=3)
+        Xtr_c, ytr_c, Xte_c, yte_c = ops.random_split(X.cpu(), y.cpu(), 0.2,
+                                                      seed=3)
         assert torch.equal(Xtr.cpu(), Xtr_c)
         assert torch.equal(Xte.cpu(), Xte_c)
+        assert torch.equal(ytr.cpu(), ytr_c)
+        assert torch.equal(yte.cpu(), yte_c)
 
     def test_large_n(self):
         y, X = ops.datagen(50_000_000, 10, seed=5, device=DEV)
