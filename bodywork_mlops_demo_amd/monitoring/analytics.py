@@ -59,6 +59,13 @@ def drift_report(store: ArtefactStore) -> dict:
                 joined["mean_response_time"].mean()
             ) if "mean_response_time" in joined else None,
         }
+        if "ks_residual" in joined:
+            # the drift monitor's columns (monitoring/drift.py)
+            report["summary"].update(
+                mean_ks_residual=float(joined["ks_residual"].mean()),
+                max_ks_residual=float(joined["ks_residual"].max()),
+                days_drifted=int(joined["drifted"].fillna(0).sum()),
+            )
     return report
 
 
@@ -72,7 +79,10 @@ def plot_drift(report: dict, path: str) -> str:
     import matplotlib.pyplot as plt
 
     j = report["joined"]
-    fig, (ax1, ax2) = plt.subplots(2, 1, figsize=(10, 6), sharex=True)
+    has_ks = "ks_residual" in j
+    fig, axes = plt.subplots(3 if has_ks else 2, 1,
+                             figsize=(10, 9 if has_ks else 6), sharex=True)
+    ax1, ax2 = axes[0], axes[1]
     ax1.plot(j["date"], j["MAPE_offline"], "o-",
              label="offline MAPE (train-time)")
     ax1.plot(j["date"], j["MAPE_online"], "s-",
@@ -85,6 +95,14 @@ def plot_drift(report: dict, path: str) -> str:
     ax2.axhline(0, color="gray", lw=0.5)
     ax2.grid(alpha=0.3)
     ax2.set_title("drift gap: online - offline MAPE")
+    if has_ks:
+        ax3 = axes[2]
+        ax3.plot(j["date"], j["ks_residual"], "o-",
+                 label="KS distance of the residuals")
+        ax3.plot(j["date"], j["ks_critical"], "r--", label="critical value")
+        ax3.legend()
+        ax3.grid(alpha=0.3)
+        ax3.set_title("residual distribution: live day vs training day")
     fig.autofmt_xdate()
     fig.savefig(path, dpi=90, bbox_inches="tight")
     plt.close(fig)

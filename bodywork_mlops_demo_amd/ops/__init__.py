@@ -12,6 +12,9 @@ here every computational primitive is a first-class gfx950 kernel
 - ``linear_score``   — batched linear scoring (stage_2:78)
 - ``regression_metrics`` — single-pass fused MAPE/R^2/max-residual
                        reduction (stage_1:79-90, stage_4:101-113)
+- ``drift_histograms`` — fused histograms of features, labels, scores and
+                       residuals for the drift monitor (no reference
+                       counterpart)
 - ``gemm_bf16``      — MFMA (v_mfma_f32_16x16x32_bf16) LDS-tiled dense
                        GEMM with fused bias+ReLU epilogue for the MLP path
 
@@ -349,6 +352,34 @@ def score_label_metrics(scores: torch.Tensor, labels: torch.Tensor) -> dict:
     var_l = s_ll - s_l * s_l / n
     corr = cov / (var_s * var_l) ** 0.5 if var_s > 0 and var_l > 0 else 0.0
     return {"MAPE": mape, "r_squared": corr, "max_residual": max_ape}
+
+
+# --------------------------------------------------------------------------
+# drift histograms — the monitoring side's one pass over stage 4's tensors
+# --------------------------------------------------------------------------
+
+def drift_histograms(
+    X: torch.Tensor, labels: torch.Tensor, scores: torch.Tensor, spec
+) -> torch.Tensor:
+    """Histograms of ``X``, ``labels``, ``scores`` and the residual
+    ``labels - scores`` in one fused 12 B/row pass.
+
+    ``spec`` is a :class:`monitoring.drift.HistSpec`; its ``bin_params()``
+    is the one place the fp32 ``(lo, scale)`` pairs are computed.  Returns
+    int64 ``[4, bins + 3]`` on the inputs' device: rows x / labels /
+    scores / residual; slot 0 underflow, ``1..bins`` the bins, ``bins + 1``
+    overflow, ``bins + 2`` NaN.  Counts are exact and bitwise
+    reproducible; the slot rule is in ``ops/hip/drift_hist.h`` and
+    mirrored by the CPU oracle.
+    """
+    lo, scale = spec.bin_params()
+    if X.device.type == "cuda":
+        core = _core(X.device)
+        return core.drift_histograms(
+            X.contiguous().float(), labels.contiguous().float(),
+            scores.contiguous().float(), int(spec.bins), lo, scale)
+    return reference.drift_histograms_cpu(X, labels, scores, int(spec.bins),
+                                          lo, scale)
 
 
 # --------------------------------------------------------------------------

@@ -26,6 +26,11 @@ at::Tensor linear_split_metrics_hip(const at::Tensor& x, const at::Tensor& y,
                                     const at::Tensor& ab, double test_frac,
                                     int64_t seed);
 at::Tensor score_label_metrics_hip(const at::Tensor& s, const at::Tensor& l);
+// drift_hist.hip
+at::Tensor drift_histograms_hip(const at::Tensor& x, const at::Tensor& labels,
+                                const at::Tensor& scores, int64_t bins,
+                                at::ArrayRef<double> lo,
+                                at::ArrayRef<double> scale);
 // mlp_small.hip
 std::tuple<at::Tensor, at::Tensor> expand1d_bf16_hip(
     const at::Tensor& x, const at::Tensor& w,
@@ -109,6 +114,8 @@ TORCH_LIBRARY(bodywork_hip, m) {
   m.def("poly_score(Tensor x, Tensor coef, float mu, float s) -> Tensor");
   m.def("regression_metrics(Tensor y, Tensor yhat) -> Tensor");
   m.def("score_label_metrics(Tensor s, Tensor l) -> Tensor");
+  m.def("drift_histograms(Tensor x, Tensor labels, Tensor scores, int bins, "
+        "float[] lo, float[] scale) -> Tensor");
   m.def("expand1d_bf16(Tensor x, Tensor w, Tensor? b, bool relu, "
         "Tensor? mask, bool emit_mask, Tensor? n_dev) -> (Tensor, Tensor)");
   m.def("rowdot_bf16(Tensor h, Tensor w, Tensor bias) -> Tensor");
@@ -160,6 +167,7 @@ TORCH_LIBRARY_IMPL(bodywork_hip, CUDA, m) {
   m.impl("poly_score", poly_score_hip);
   m.impl("regression_metrics", regression_metrics_hip);
   m.impl("score_label_metrics", score_label_metrics_hip);
+  m.impl("drift_histograms", drift_histograms_hip);
   m.impl("expand1d_bf16", expand1d_bf16_hip);
   m.impl("rowdot_bf16", rowdot_bf16_hip);
   m.impl("coldot_bf16", coldot_bf16_hip);

@@ -187,6 +187,43 @@ def score_label_sums_cpu(scores: torch.Tensor, labels: torch.Tensor):
 
 
 # --------------------------------------------------------------------------
+# drift histograms oracle
+# --------------------------------------------------------------------------
+
+def drift_histograms_cpu(x, labels, scores, bins: int, lo, scale) -> torch.Tensor:
+    """int64 ``[4, bins + 3]`` histograms of ``x``, ``labels``, ``scores``
+    and the residual ``labels - scores`` — the oracle of
+    ``ops/hip/drift_hist.hip`` and the CPU path of
+    :func:`ops.drift_histograms`.
+
+    The slot rule of ``ops/hip/drift_hist.h`` in numpy float32, one
+    rounded fp32 operation per step: ``t = (v - lo_k) * scale_k``; slot
+    ``bins + 2`` if ``t`` is NaN, else 0 if ``t < 0``, else ``bins + 1``
+    if ``t >= bins``, else ``1 + trunc(t)``.  ``lo`` / ``scale`` hold one
+    fp32 value per row."""
+    def f32(v):
+        if torch.is_tensor(v):
+            v = v.detach().cpu().numpy()
+        return np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
+
+    xv, lv, sv = f32(x), f32(labels), f32(scores)
+    out = np.zeros((4, bins + 3), dtype=np.int64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        rows = (xv, lv, sv, lv - sv)
+        for k, v in enumerate(rows):
+            t = (v - np.float32(lo[k])) * np.float32(scale[k])
+            slot = np.full(t.shape, bins + 2, dtype=np.int64)  # NaN
+            under = t < np.float32(0)
+            over = t >= np.float32(bins)
+            inside = ~(under | over | np.isnan(t))
+            slot[inside] = 1 + t[inside].astype(np.int64)  # truncation
+            slot[under] = 0
+            slot[over] = bins + 1
+            out[k] = np.bincount(slot, minlength=bins + 3)
+    return torch.from_numpy(out)
+
+
+# --------------------------------------------------------------------------
 # GEMM oracle
 # --------------------------------------------------------------------------
 

@@ -263,6 +263,7 @@ def run_cycle(
     http_mode: str = "binary",
     http_port: int = 5600,
     capture: dict | None = None,
+    drift_monitor=None,
 ) -> dict:
     """Run one full cycle; returns per-phase timings + metrics.
 
@@ -283,6 +284,12 @@ def run_cycle(
     ``capture``, when given, receives references to what this cycle
     computed beyond the returned metrics: the trained ``model`` and the
     day-t+1 ``X``/``labels``/``scores`` tensors of stage 4.
+
+    ``drift_monitor`` (a :class:`monitoring.drift.DriftMonitor`): after a
+    training — not in a ``skip_train`` cycle — its reference becomes the
+    newest training day scored by the freshly trained model (inside
+    ``train_s``), and stage 4 observes day t+1 against it: the statistics
+    join ``online`` and the test-metrics CSV.
     """
     device = state.device
     dev_cuda = device.startswith("cuda")
@@ -323,10 +330,12 @@ def run_cycle(
             return _finish_cycle(state, store, n_rows, persist_fmt, None,
                                  timings, metrics, sync,
                                  http=(replica.url, http_mode),
-                                 capture=capture)
+                                 capture=capture,
+                                 drift_monitor=drift_monitor)
         scorer = scorer_cache["scorer"]
         return _finish_cycle(state, store, n_rows, persist_fmt, scorer,
-                             timings, metrics, sync, capture=capture)
+                             timings, metrics, sync, capture=capture,
+                             drift_monitor=drift_monitor)
     metrics, trained = stage1.run(
         eff_store,
         model_type=model_type,
@@ -340,6 +349,12 @@ def run_cycle(
         return_model=True,
         model_cache=scorer_cache,
     )
+    if drift_monitor is not None:
+        # reference distribution: the newest training day as the model
+        # that was just fitted to it scores it
+        day = state._day_sizes[-1]
+        X_day, y_day = state.X[-day:], state.y[-day:]
+        drift_monitor.set_reference(X_day, y_day, trained.predict(X_day))
     sync()
     timings["train_s"] = perf_counter() - t0
     if capture is not None:
@@ -378,7 +393,8 @@ def run_cycle(
         timings["deploy_s"] = perf_counter() - t0
         return _finish_cycle(state, store, n_rows, persist_fmt, None,
                              timings, metrics, sync,
-                             http=(replica.url, http_mode), capture=capture)
+                             http=(replica.url, http_mode), capture=capture,
+                             drift_monitor=drift_monitor)
     if store is not None:
         if process_group is not None:  # rank 0 persisted; others wait
             import torch.distributed as dist
@@ -415,12 +431,13 @@ def run_cycle(
     timings["deploy_s"] = perf_counter() - t0
 
     return _finish_cycle(state, store, n_rows, persist_fmt, scorer, timings,
-                         metrics, sync, capture=capture)
+                         metrics, sync, capture=capture,
+                         drift_monitor=drift_monitor)
 
 
 def _finish_cycle(state, store, n_rows, persist_fmt, scorer, timings,
                   metrics, sync, http: tuple[str, str] | None = None,
-                  capture: dict | None = None):
+                  capture: dict | None = None, drift_monitor=None):
     """Stages 3+4 and clock advance (shared by train and skip-train paths).
 
     ``http=(url, mode)`` routes stage 4 over the wire to a live replica
@@ -450,6 +467,7 @@ def _finish_cycle(state, store, n_rows, persist_fmt, scorer, timings,
             data=(y_next, X_next, next_date),
             persist=store is not None and state.rank == 0,
             capture=capture,
+            drift_monitor=drift_monitor,
         )
     else:
         test_metrics = stage4.run(
@@ -459,6 +477,7 @@ def _finish_cycle(state, store, n_rows, persist_fmt, scorer, timings,
             data=(y_next, X_next, next_date),
             persist=store is not None and state.rank == 0,
             capture=capture,
+            drift_monitor=drift_monitor,
         )
     sync()
     timings["test_s"] = perf_counter() - t0

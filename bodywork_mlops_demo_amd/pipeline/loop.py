@@ -38,6 +38,9 @@ def run_loop(
     resume: bool = True,
     retrain_policy: str = "always",
     drift_threshold: float = 1.5,
+    drift_monitor: bool = False,
+    ks_alpha: float = 1e-3,
+    ks_threshold: float | None = None,
 ) -> list[dict]:
     """Run ``days`` cycles.
 
@@ -47,6 +50,15 @@ def run_loop(
       while its live MAPE stays below ``drift_threshold`` x its own
       offline MAPE at training time; retrain only when the online
       metrics show the concept has drifted away from it.
+    - ``"ks"``     — retrain when the drift monitor says so: the KS
+      distance between the residual distribution of the live day and that
+      of the newest training day exceeds the two-sample critical value at
+      level ``ks_alpha`` (and ``ks_threshold``, when given).  Implies
+      ``drift_monitor``.
+
+    ``drift_monitor`` adds the monitor's statistics
+    (:mod:`monitoring.drift`) to every cycle's ``online`` dict and
+    test-metrics CSV row without changing the policy.
     """
     device = device or ("cuda" if torch.cuda.is_available() else "cpu")
     if isinstance(start_date, str):
@@ -82,19 +94,30 @@ def run_loop(
         except FileNotFoundError:
             pass
 
+    monitor = None
+    if drift_monitor or retrain_policy == "ks":
+        from bodywork_mlops_demo_amd.monitoring.drift import DriftMonitor
+
+        monitor = DriftMonitor(alpha=ks_alpha, ks_threshold=ks_threshold,
+                               process_group=process_group)
+
     results = []
     scorer_cache: dict = {}
     drifted = True  # first day always trains
     for day in range(days):
-        skip = retrain_policy == "drift" and not drifted
+        skip = retrain_policy in ("drift", "ks") and not drifted
         r = run_cycle(
             state, store, n_rows, model_type=model_type,
             process_group=process_group, persist_fmt=persist_fmt,
             scorer_cache=scorer_cache, skip_train=skip,
+            drift_monitor=monitor,
         )
         results.append(r)
-        offline_mape = (r["offline"] or {}).get("MAPE", float("inf"))
-        drifted = r["online"]["MAPE"] > drift_threshold * offline_mape
+        if retrain_policy == "ks":
+            drifted = r["online"]["drifted"]
+        else:
+            offline_mape = (r["offline"] or {}).get("MAPE", float("inf"))
+            drifted = r["online"]["MAPE"] > drift_threshold * offline_mape
         if process_group is not None:
             # collective decision: every rank must take the same
             # train/skip branch next cycle (a rank-local decision would
@@ -117,8 +140,8 @@ def run_loop(
             f"test {t['test_s']:.3f}) online MAPE "
             f"{r['online']['MAPE']:.4f}"
             + (" [retrain skipped: no drift]" if skip else "")
-            + (" [drift detected]" if drifted and retrain_policy == "drift"
-               else "")
+            + (" [drift detected]"
+               if drifted and retrain_policy in ("drift", "ks") else "")
         )
     state.drain_io()
     return results
@@ -159,8 +182,16 @@ def main(argv=None) -> None:
     p.add_argument("--format", default="csv", choices=["csv", "npy"])
     p.add_argument("--json-out", default=None)
     p.add_argument("--retrain-policy", default="always",
-                   choices=["always", "drift"])
+                   choices=["always", "drift", "ks"])
     p.add_argument("--drift-threshold", type=float, default=1.5)
+    p.add_argument("--drift-monitor", action="store_true",
+                   help="add the PSI/KS drift statistics to the online "
+                        "metrics (implied by --retrain-policy ks)")
+    p.add_argument("--ks-alpha", type=float, default=1e-3,
+                   help="level of the two-sample KS test on the residuals")
+    p.add_argument("--ks-threshold", type=float, default=None,
+                   help="additional floor on the KS distance that counts "
+                        "as drift")
     args = p.parse_args(argv)
     # env flags so the models built inside the cycle opt in
     args.model, env = resolve_model(args.model)
@@ -174,6 +205,8 @@ def main(argv=None) -> None:
         start_date=args.start_date, persist_fmt=args.format,
         retrain_policy=args.retrain_policy,
         drift_threshold=args.drift_threshold,
+        drift_monitor=args.drift_monitor, ks_alpha=args.ks_alpha,
+        ks_threshold=args.ks_threshold,
     )
     if args.json_out:
         with open(args.json_out, "w") as f:

@@ -150,8 +150,15 @@ def run(
     data: tuple[torch.Tensor, torch.Tensor, date_t] | None = None,
     persist: bool = True,
     capture: dict | None = None,
+    drift_monitor=None,
 ) -> dict:
     """Score the latest dataset against the service; persist test metrics.
+
+    ``drift_monitor`` (a :class:`monitoring.drift.DriftMonitor` with its
+    reference set) observes the tensors held here; its statistics join the
+    returned metrics and are appended as columns to the test-metrics CSV.
+    Without one the metrics and the CSV are unchanged.
+
 
     ``scorer`` bypasses HTTP entirely (in-process serving replica) for the
     hermetic pipeline/bench path; ``data`` skips the store read when the
@@ -204,19 +211,29 @@ def run(
     metrics["mean_response_time"] = mean_rt
     metrics["response_time_kind"] = rt_kind
     metrics["rows_per_sec"] = n / (mean_rt * n) if mean_rt > 0 else float("inf")
+    drift_keys: tuple = ()
+    if drift_monitor is not None:
+        from bodywork_mlops_demo_amd.monitoring.drift import METRIC_KEYS
+
+        metrics.update(drift_monitor.observe(X.to(device), labels, scores))
+        drift_keys = METRIC_KEYS
     log.info(f"live-service metrics on {n} rows: {metrics}")
 
     if persist:
         key = contract.test_metrics_key(data_date)
         # reference schema (stage_4:106-112) + a kind column so the
-        # amortised in-process figure can never be read as a latency
+        # amortised in-process figure can never be read as a latency;
+        # the drift monitor's columns, when there is one, come last
         store.put_metrics_csv(
             key,
             ["date", "MAPE", "r_squared", "max_residual",
-             "mean_response_time", "response_time_kind"],
+             "mean_response_time", "response_time_kind", *drift_keys],
             [data_date, metrics["MAPE"], metrics["r_squared"],
              metrics["max_residual"], metrics["mean_response_time"],
-             rt_kind],
+             rt_kind,
+             # the decision as 0/1 so the analytics read it as a number
+             *(int(metrics[k]) if k == "drifted" else metrics[k]
+               for k in drift_keys)],
         )
         log.info(f"uploaded test metrics to {key}")
     return metrics

@@ -22,6 +22,7 @@ sources = [
     os.path.join(HIP_DIR, "bindings.cpp"),
     os.path.join(HIP_DIR, "datagen.hip"),
     os.path.join(HIP_DIR, "linreg.hip"),
+    os.path.join(HIP_DIR, "drift_hist.hip"),
     os.path.join(HIP_DIR, "mlp_small.hip"),
     os.path.join(HIP_DIR, "gemm.hip"),
     os.path.join(HIP_DIR, "gemm8.hip"),
