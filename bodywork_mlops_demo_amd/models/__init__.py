@@ -1,6 +1,9 @@
 from bodywork_mlops_demo_amd.models.linear import GPULinearRegressor  # noqa: F401
 from bodywork_mlops_demo_amd.models.mlp import GPUMLPRegressor  # noqa: F401
-from bodywork_mlops_demo_amd.models.poly import GPUPolyRegressor  # noqa: F401
+from bodywork_mlops_demo_amd.models.poly import (  # noqa: F401
+    GPUPolyRegressor,
+    GPUPolyRegressorCV,
+)
 
 
 def regressor_from_artifact(obj, device="cpu"):

@@ -136,3 +136,69 @@ class GPUPolyRegressor:
     def __repr__(self) -> str:
         return (f"Pipeline(PolynomialFeatures(degree={self.degree}), "
                 f"Ridge(alpha={self.l2}))")
+
+
+class GPUPolyRegressorCV(GPUPolyRegressor):
+    """:class:`GPUPolyRegressor` that picks ``degree`` and ``l2`` itself by
+    K-fold cross-validation — the ``RidgeCV`` / ``GridSearchCV`` of this
+    family, at the cost of ONE statistics pass.
+
+    ``ops.poly_fold_stats`` reduces (X, y) to 18 sums per fold; from those
+    ``ops.select_poly`` scores every (degree <= ``max_degree``, l2 in
+    ``l2_grid``) candidate on every held-out fold and solves the winner
+    from all rows.  After ``fit`` the object IS a fitted
+    ``GPUPolyRegressor`` of the chosen degree: scoring, the sklearn
+    artefact and hot-redeploy are inherited (a redeploy onto a scorer of
+    another degree is refused by ``copy_weights_from``, so the caller
+    builds a fresh scorer).
+
+    ``best_params_`` is ``{"degree", "l2"}``, ``best_score_`` the winner's
+    held-out MSE and ``cv_results_`` the whole grid as parallel lists
+    ``degree`` / ``l2`` / ``mean_test_mse`` (``inf``: not solvable).
+    """
+
+    def __init__(self, max_degree: int = 5,
+                 l2_grid=(0.0, 1e-6, 1e-4, 1e-2, 1.0), folds: int = 5,
+                 seed: int = 42, device="cpu"):
+        if not 1 <= max_degree <= 5:
+            raise ValueError("max_degree must be in [1, 5]")
+        if not 2 <= folds <= 5:
+            raise ValueError("folds must be in [2, 5]")
+        l2_grid = tuple(float(v) for v in l2_grid)
+        if not l2_grid or min(l2_grid) < 0:
+            raise ValueError("l2_grid needs at least one value, all >= 0")
+        super().__init__(degree=max_degree, l2=l2_grid[0], device=device)
+        self.max_degree = max_degree
+        self.l2_grid = l2_grid
+        self.folds = folds
+        self.seed = seed
+        self.best_params_: dict | None = None
+        self.best_score_: float | None = None
+        self.cv_results_: dict | None = None
+
+    def fit(self, X: torch.Tensor, y: torch.Tensor, process_group=None):
+        stats = ops.poly_fold_stats(X, y, self.folds, self.seed, self.X_MU,
+                                    self.X_SIGMA)
+        if process_group is not None:
+            import torch.distributed as dist
+
+            dist.all_reduce(stats, group=process_group)
+        return self._select(stats)
+
+    def _select(self, fold_stats: torch.Tensor):
+        degrees = list(range(1, self.max_degree + 1))
+        sel = ops.select_poly(fold_stats, degrees, self.l2_grid)
+        if sel.degree != self.degree:
+            self._coef_dev = None  # another length: rebuilt on next use
+        self.degree, self.l2, self.coef_t_ = sel.degree, sel.l2, sel.coef
+        self._sync_dev()
+        self.best_params_ = {"degree": sel.degree, "l2": sel.l2}
+        self.best_score_ = float(
+            sel.scores[degrees.index(sel.degree),
+                       self.l2_grid.index(sel.l2)])
+        self.cv_results_ = {
+            "degree": [d for d in degrees for _ in self.l2_grid],
+            "l2": [v for _ in degrees for v in self.l2_grid],
+            "mean_test_mse": sel.scores.reshape(-1).tolist(),
+        }
+        return self

@@ -9,6 +9,10 @@ here every computational primitive is a first-class gfx950 kernel
                        in-kernel y>=0 stream compaction (stage_3:28-43)
 - ``linreg_stats``   — fused XtX/Xty statistics reduction for the
                        closed-form OLS fit (stage_1:105-106)
+- ``poly_fold_stats`` — per-fold power sums: K-fold cross-validation of
+                       every polynomial degree and l2 from one pass (no
+                       reference counterpart; ``select_poly`` is the host
+                       side)
 - ``linear_score``   — batched linear scoring (stage_2:78)
 - ``regression_metrics`` — single-pass fused MAPE/R^2/max-residual
                        reduction (stage_1:79-90, stage_4:101-113)
@@ -28,7 +32,9 @@ from __future__ import annotations
 
 import glob
 import os
+from typing import NamedTuple
 
+import numpy as np
 import torch
 
 from bodywork_mlops_demo_amd.ops import reference
@@ -190,8 +196,6 @@ def solve_poly(
 ) -> list[float]:
     """Normalised-basis coefficients from fused stats (host-side solve;
     the intercept term is not penalised)."""
-    import numpy as np
-
     nf = degree + 1
     tri = nf * (nf + 1) // 2
     vals = stats.cpu().numpy()
@@ -207,6 +211,121 @@ def solve_poly(
         reg[0, 0] = 0.0  # do not penalise the intercept
         A = A + reg
     return np.linalg.solve(A, bvec).tolist()
+
+
+def poly_fold_stats(
+    X: torch.Tensor,
+    y: torch.Tensor,
+    folds: int = 5,
+    seed: int = 42,
+    mu: float = 50.0,
+    s: float = 50.0,
+) -> torch.Tensor:
+    """Per-fold sufficient statistics for K-fold cross-validation of every
+    polynomial degree 1..5 and every ``l2``, in ONE 8 B/row pass.
+
+    Returns fp64 ``[folds, 18]`` on the inputs' device; row f is
+    ``[S_0..S_10, T_0..T_5, Q]`` over the rows of fold f with ``S_p = sum
+    t^p`` (``S_0`` is the fold's row count), ``T_q = sum y t^q``, ``Q =
+    sum y^2`` and ``t = (x-mu)/s`` as in :func:`poly_stats`.  Row i is in
+    fold ``(philox(seed, i).x * folds) >> 32`` (a stream of its own).  The
+    rows add, so this tensor is the whole DP all-reduce payload;
+    :func:`select_poly` turns it into a model.  ``2 <= folds <= 5``.
+    """
+    if not 2 <= int(folds) <= 5:
+        raise ValueError("poly_fold_stats: folds must be in [2, 5]")
+    if X.device.type == "cuda":
+        core = _core(X.device)
+        return core.poly_fold_stats(X.contiguous().float(),
+                                    y.contiguous().float(), int(folds),
+                                    int(seed), mu, s)
+    return reference.poly_fold_stats_cpu(X, y, int(folds), int(seed), mu, s)
+
+
+class PolySelection(NamedTuple):
+    """What :func:`select_poly` returns."""
+
+    degree: int
+    l2: float
+    coef: list[float]      # normalised basis, solved from all rows
+    scores: np.ndarray     # [len(degrees), len(l2_grid)] held-out MSE
+
+
+def select_poly(fold_stats: torch.Tensor, degrees, l2_grid) -> PolySelection:
+    """K-fold model selection over ``degrees`` x ``l2_grid`` from
+    :func:`poly_fold_stats` output — host-side, a few batched small solves.
+
+    For the basis ``t^j`` the Gram matrix is the Hankel matrix ``H[a, b] =
+    S_{a+b}`` and the squared error of coefficients b on a row set is ``Q
+    - 2 bT T + bT H b``.  Per candidate and fold f the training system is
+    total minus fold f with :func:`solve_poly`'s ridge convention (penalty
+    ``l2 * n_train``, intercept unpenalised); the score is ``sum_f SSE_f /
+    sum_f n_f``.  A candidate with a singular training system, or one with
+    fewer rows than coefficients, scores ``inf``; if all do, ValueError.
+    The smallest score wins; exact ties go to the lower degree, then the
+    larger ``l2``.  The chosen candidate is then solved from the total.
+    """
+    fs = np.asarray(fold_stats.detach().cpu().numpy(), dtype=np.float64)
+    max_deg = reference.POLY_FOLD_MAXDEG
+    if fs.ndim != 2 or fs.shape[1] != reference.POLY_FOLD_K:
+        raise ValueError("select_poly: fold_stats must be [folds, 18]")
+    degrees = [int(d) for d in degrees]
+    l2s = np.asarray([float(v) for v in l2_grid], dtype=np.float64)
+    if (not degrees or l2s.size == 0 or (l2s < 0).any()
+            or not all(1 <= d <= max_deg for d in degrees)):
+        raise ValueError("select_poly: needs degrees in [1, 5] and l2 >= 0")
+    ns = 2 * max_deg + 1
+    total = fs.sum(axis=0)
+    train = total[None, :] - fs  # [F, 18]
+    n_val, n_train = fs[:, 0], train[:, 0]
+
+    def system(rows, nf):
+        # Hankel Gram matrices [.., nf, nf], moments [.., nf]
+        idx = np.arange(nf)[:, None] + np.arange(nf)[None, :]
+        return rows[..., :ns][..., idx], rows[..., ns:ns + nf]
+
+    def ridge(H, n, nf):
+        # [L, .., nf, nf]: H + l2 * n * diag(0, 1, .., 1)
+        pen = np.eye(nf)
+        pen[0, 0] = 0.0
+        scale = l2s.reshape((-1,) + (1,) * (H.ndim - 2)) * n
+        return H[None] + scale[..., None, None] * pen
+
+    scores = np.full((len(degrees), l2s.size), np.inf)
+    for i, d in enumerate(degrees):
+        nf = d + 1
+        H_tr, T_tr = system(train, nf)
+        H_va, T_va = system(fs, nf)
+        A = ridge(H_tr, n_train, nf)                       # [L, F, nf, nf]
+        rhs = np.broadcast_to(T_tr[None, :, :, None], A.shape[:-1] + (1,))
+        ok = np.broadcast_to(n_train >= nf, A.shape[:2]).copy()
+        b = np.zeros(A.shape[:-1])
+        try:
+            b[:] = np.linalg.solve(A, rhs)[..., 0]
+        except np.linalg.LinAlgError:
+            # some system is singular: find which, one by one
+            for li, f in np.ndindex(*A.shape[:2]):
+                try:
+                    b[li, f] = np.linalg.solve(A[li, f], rhs[li, f, :, 0])
+                except np.linalg.LinAlgError:
+                    ok[li, f] = False
+        sse = (fs[None, :, -1] - 2.0 * np.einsum("lfa,fa->lf", b, T_va)
+               + np.einsum("lfa,fab,lfb->lf", b, H_va, b))
+        with np.errstate(invalid="ignore"):
+            score = sse.sum(axis=1) / n_val.sum()
+        score[~ok.all(axis=1) | ~np.isfinite(score)] = np.inf
+        scores[i] = score
+    if not np.isfinite(scores).any():
+        raise ValueError(
+            "select_poly: no candidate has a solvable training system in "
+            "every fold (too few rows?)")
+    best = min(
+        ((scores[i, j], degrees[i], -l2s[j], i, j)
+         for i in range(len(degrees)) for j in range(l2s.size)))
+    _, degree, _, i, j = best
+    H, T = system(total, degree + 1)
+    coef = np.linalg.solve(ridge(H, total[0], degree + 1)[j], T)
+    return PolySelection(degree, float(l2s[j]), coef.tolist(), scores)
 
 
 def poly_score(

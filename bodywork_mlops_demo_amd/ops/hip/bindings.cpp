@@ -19,6 +19,10 @@ at::Tensor linear_score_hip(const at::Tensor& x, const at::Tensor& ab,
                             const c10::optional<at::Tensor>& n_dev);
 at::Tensor poly_stats_hip(const at::Tensor& x, const at::Tensor& y,
                           int64_t nf, double mu, double s);
+at::Tensor poly_fold_stats_hip(const at::Tensor& x, const at::Tensor& y,
+                               int64_t folds, int64_t seed, double mu,
+                               double s);
+at::Tensor reduce_finalize_hip(const at::Tensor& ws, bool wide);
 at::Tensor poly_score_hip(const at::Tensor& x, const at::Tensor& coef,
                           double mu, double s);
 at::Tensor regression_metrics_hip(const at::Tensor& y, const at::Tensor& yhat);
@@ -111,6 +115,9 @@ TORCH_LIBRARY(bodywork_hip, m) {
   m.def("linear_split_metrics(Tensor x, Tensor y, Tensor ab, "
         "float test_frac, int seed) -> Tensor");
   m.def("poly_stats(Tensor x, Tensor y, int nf, float mu, float s) -> Tensor");
+  m.def("poly_fold_stats(Tensor x, Tensor y, int folds, int seed, float mu, "
+        "float s) -> Tensor");
+  m.def("reduce_finalize(Tensor ws, bool wide) -> Tensor");
   m.def("poly_score(Tensor x, Tensor coef, float mu, float s) -> Tensor");
   m.def("regression_metrics(Tensor y, Tensor yhat) -> Tensor");
   m.def("score_label_metrics(Tensor s, Tensor l) -> Tensor");
@@ -164,6 +171,8 @@ TORCH_LIBRARY_IMPL(bodywork_hip, CUDA, m) {
   m.impl("linear_score", linear_score_hip);
   m.impl("linear_split_metrics", linear_split_metrics_hip);
   m.impl("poly_stats", poly_stats_hip);
+  m.impl("poly_fold_stats", poly_fold_stats_hip);
+  m.impl("reduce_finalize", reduce_finalize_hip);
   m.impl("poly_score", poly_score_hip);
   m.impl("regression_metrics", regression_metrics_hip);
   m.impl("score_label_metrics", score_label_metrics_hip);

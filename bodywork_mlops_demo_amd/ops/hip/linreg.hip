@@ -13,13 +13,18 @@
 //   - linreg_split_stats / linear_split_metrics: the same two passes with
 //     the philox train/test flag of random_split evaluated in-kernel, so
 //     the linear fit never materialises the split.
+//   - poly_stats / poly_fold_stats: the same for the polynomial ridge
+//     family — the implicit-basis X^T X / X^T y of one degree, and the 18
+//     power sums per cross-validation fold that carry the K-fold CV of
+//     every degree <= 5 and every l2.
 // All reductions are two-stage and atomic-free: per-wave shuffle -> LDS ->
 // one plain store per block and statistic into a [grid, K] fp64 workspace,
-// then a one-block finalise kernel that combines the partials in a fixed
-// order.  (One fp64 atomic per block and statistic into the same few
-// addresses costs ~12 ns each on MI355X — 250 us for an 80 MB pass that
-// streams in 19 us — and makes the sums depend on arrival order; the
-// two-stage form is bitwise reproducible.)  Accumulation in fp64 so
+// then a finalise kernel (one block, or one block per statistic where K is
+// large) that combines the partials in a fixed order.  (One fp64 atomic
+// per block and statistic into the same few addresses costs ~12 ns each on
+// MI355X — 250 us for an 80 MB pass that streams in 19 us — and makes the
+// sums depend on arrival order; the two-stage form is bitwise
+// reproducible.)  Accumulation in fp64 so
 // 1B-row sums stay exact to ~2^-40.  Stage 1 of the streaming reductions
 // is one kernel (stream_reduce.h) instantiated over the statistic types
 // below; two_stage_reduce is the one host driver.
@@ -71,22 +76,55 @@ __global__ void reduce_finalize_kernel(const double* __restrict__ ws,
   if (off == 1 && threadIdx.x == 0) out[0] = n;
 }
 
+// The wide finalise, for a K too large to walk in one block (the one-block
+// kernel is latency-bound per statistic): block k owns statistic k and
+// combines its partials exactly as reduce_finalize_kernel does, so the two
+// give the same bits.  Sums only.
+__global__ void reduce_finalize_wide_kernel(const double* __restrict__ ws,
+                                            double* __restrict__ out,
+                                            int nblocks, int K, int off,
+                                            double n) {
+  __shared__ double lds[RED_WAVES];
+  const int k = blockIdx.x;
+  double v = 0.0;
+  for (int g = threadIdx.x; g < nblocks; g += RED_BLOCK)
+    v += ws[(long long)g * K + k];
+  v = block_sum_f64<RED_WAVES>(v, lds);
+  if (threadIdx.x == 0) {
+    out[off + k] = v;
+    if (off == 1 && k == 0) out[0] = n;
+  }
+}
+
+static void launch_finalize(const double* ws, double* out, int nblocks, int K,
+                            unsigned int max_mask, int off, double n,
+                            bool wide, hipStream_t stream) {
+  if (wide) {
+    TORCH_CHECK(max_mask == 0u, "the wide finalise combines sums only");
+    hipLaunchKernelGGL(reduce_finalize_wide_kernel, dim3(K), dim3(RED_BLOCK),
+                       0, stream, ws, out, nblocks, K, off, n);
+  } else {
+    hipLaunchKernelGGL(reduce_finalize_kernel, dim3(1), dim3(RED_BLOCK), 0,
+                       stream, ws, out, nblocks, K, max_mask, off, n);
+  }
+}
+
 // Both stages of a reduction over n rows on `like`'s device: grid ->
 // workspace -> stage 1 -> finalise.  launch(grid, ws, stream) starts the
-// stage-1 kernel, which fills ws[grid, K].
+// stage-1 kernel, which fills ws[grid, K].  `wide` picks the
+// block-per-statistic finalise.
 template <class Launch>
 static at::Tensor two_stage_reduce(const at::Tensor& like, long long n,
                                    int per_thread, int K,
                                    unsigned int max_mask, int off,
-                                   Launch launch) {
+                                   Launch launch, bool wide = false) {
   const int grid = capped_grid(n, RED_GRID_CAP, per_thread);
   auto ws = at::empty({(long long)grid * K}, like.options().dtype(at::kDouble));
   auto stream = at::cuda::getCurrentCUDAStream();
   launch(grid, ws.data_ptr<double>(), stream);
   auto out = at::empty({off + K}, ws.options());
-  hipLaunchKernelGGL(reduce_finalize_kernel, dim3(1), dim3(RED_BLOCK), 0,
-                     stream, ws.data_ptr<double>(), out.data_ptr<double>(),
-                     grid, K, max_mask, off, (double)n);
+  launch_finalize(ws.data_ptr<double>(), out.data_ptr<double>(), grid, K,
+                  max_mask, off, (double)n, wide, stream);
   return out;
 }
 
@@ -274,6 +312,121 @@ at::Tensor poly_stats_hip(const at::Tensor& x, const at::Tensor& y,
         }
 #undef PS_LAUNCH
       });
+}
+
+// ---- poly_fold_stats: K-fold statistics of every degree 1..5 in one pass --
+// For the basis phi_j = t^j, PhiT Phi is the Hankel matrix of the power
+// sums S_p = sum t^p, PhiT y is T_q = sum y t^q, and the squared error of
+// any coefficient vector b on any row subset is Q - 2 bT T + bT H b with
+// Q = sum y^2.  So per fold the PF_K = 18 sums
+//   [S_0..S_10, T_0..T_5, Q]            (S_0 = the fold's row count)
+// hold the complete K-fold cross-validation of every degree <= 5 and every
+// l2: training statistics of fold f = total - fold f.  out is [F, PF_K].
+// Row i belongs to fold_of_row(key, i, F) (philox.h).
+#define PF_MAXDEG 5
+#define PF_NS (2 * PF_MAXDEG + 1)          // S_0..S_10
+#define PF_K (PF_NS + PF_MAXDEG + 1 + 1)   // + T_0..T_5 + Q
+
+// Keeps a loop of its own like poly_stats_kernel.  acc[F * PF_K] lives in
+// registers (F = 5: 180 of the 256 a 2-waves/SIMD kernel may hold, which
+// is why F stops at 5); a row is folded into every fold's accumulators
+// with a 0/1 weight, so there is no divergence and no indexed register
+// access.  t and its powers round exactly as in poly_stats_kernel.
+template <int F>
+__global__ void __launch_bounds__(RED_BLOCK)
+poly_fold_stats_kernel(const float* __restrict__ x,
+                       const float* __restrict__ y, double* __restrict__ ws,
+                       long long n, float mu, float inv_s, PhiloxKey key) {
+  static_assert(RED_WAVES == 4, "the block tail below combines 4 waves");
+  constexpr int K = F * PF_K;
+  double acc[K];  // [F][PF_K]
+#pragma unroll
+  for (int k = 0; k < K; ++k) acc[k] = 0.0;
+  const long long stride = (long long)gridDim.x * RED_BLOCK;
+  for (long long j = (long long)blockIdx.x * RED_BLOCK + threadIdx.x; j < n;
+       j += stride) {
+    const double t = (double)((x[j] - mu) * inv_s);
+    const double yv = y[j];
+    double v[PF_K];
+    v[0] = 1.0;
+#pragma unroll
+    for (int p = 1; p < PF_NS; ++p) v[p] = v[p - 1] * t;
+#pragma unroll
+    for (int q = 0; q <= PF_MAXDEG; ++q) v[PF_NS + q] = yv * v[q];
+    v[PF_K - 1] = yv * yv;
+    const unsigned int fold = fold_of_row(key, (unsigned long long)j, F);
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+      const double w = fold == (unsigned int)f ? 1.0 : 0.0;
+#pragma unroll
+      for (int k = 0; k < PF_K; ++k)
+        acc[f * PF_K + k] = fma(w, v[k], acc[f * PF_K + k]);
+    }
+  }
+  // block tail: all K statistics through one LDS array and ONE barrier
+  // (block_reduce_store would take two per statistic, and a full shuffle
+  // butterfly each).  wave_sum_scatter_f64 gives the bits of wave_sum_f64;
+  // the four wave sums then combine as (w0 + w2) + (w1 + w3), which is
+  // what block_sum_f64's xor butterfly computes.
+  __shared__ double lds[RED_WAVES][K];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  wave_sum_scatter_f64<K>(acc, lane);
+#pragma unroll
+  for (int e = 0; e < wave_scatter_len<K>(); ++e) {
+    const int k = wave_scatter_index<K>(e, lane);
+    if (k >= 0) lds[wave][k] = acc[e];
+  }
+  __syncthreads();
+  if (threadIdx.x < K) {
+    const int k = threadIdx.x;
+    ws[(long long)blockIdx.x * K + k] =
+        (lds[0][k] + lds[2][k]) + (lds[1][k] + lds[3][k]);
+  }
+}
+
+at::Tensor poly_fold_stats_hip(const at::Tensor& x, const at::Tensor& y,
+                               int64_t folds, int64_t seed, double mu,
+                               double s) {
+  check_xy(x, y);
+  TORCH_CHECK(folds >= 2 && folds <= 5, "poly_fold_stats: 2 <= folds <= 5");
+  const long long n = x.numel();
+  if (n == 0)
+    return at::zeros({folds, PF_K}, x.options().dtype(at::kDouble));
+  const float inv_s = (float)(1.0 / s);
+  const PhiloxKey key = fold_key(seed);
+  // one row per thread and sweep, as poly_stats
+  return two_stage_reduce(
+             x, n, 1, (int)folds * PF_K, 0u, 0,
+             [&](int grid, double* ws, hipStream_t stream) {
+#define PF_LAUNCH(F_)                                                     \
+  hipLaunchKernelGGL((poly_fold_stats_kernel<F_>), dim3(grid),            \
+                     dim3(RED_BLOCK), 0, stream, x.data_ptr<float>(),     \
+                     y.data_ptr<float>(), ws, n, (float)mu, inv_s, key)
+               switch (folds) {
+                 case 2: PF_LAUNCH(2); break;
+                 case 3: PF_LAUNCH(3); break;
+                 case 4: PF_LAUNCH(4); break;
+                 default: PF_LAUNCH(5); break;
+               }
+#undef PF_LAUNCH
+             },
+             /*wide=*/true)
+      .view({folds, PF_K});
+}
+
+// Stage 2 alone over a [nblocks, K] fp64 workspace of sums, through the
+// one-block or the wide finalise: the two give the same bits, which is
+// what the tests and the A/B timing of the two kernels use this for.
+at::Tensor reduce_finalize_hip(const at::Tensor& ws, bool wide) {
+  TORCH_CHECK(ws.is_cuda() && ws.scalar_type() == at::kDouble &&
+              ws.dim() == 2 && ws.is_contiguous() && ws.size(0) >= 1 &&
+              ws.size(1) >= 1, "reduce_finalize: ws is a contiguous fp64 "
+              "[nblocks, K] device tensor");
+  auto out = at::empty({ws.size(1)}, ws.options());
+  launch_finalize(ws.data_ptr<double>(), out.data_ptr<double>(),
+                  (int)ws.size(0), (int)ws.size(1), 0u, 0, 0.0, wide,
+                  at::cuda::getCurrentCUDAStream());
+  return out;
 }
 
 // Horner-scheme polynomial scoring in the normalised basis; coefficients

@@ -42,11 +42,12 @@ __device__ __forceinline__ Philox4 philox4x32(unsigned long long counter,
   return {c0, c1, c2, c3};
 }
 
-// ---- the project's two philox streams, side by side -----------------------
+// ---- the project's philox streams, side by side ---------------------------
 // key = (lo32(seed), hi32(seed)); a seed that fits 32 bits takes the
-// stream's own default second key word instead, so the data generator and
-// the train/test split never draw from the same stream for one seed
-// (ops/reference.py: datagen_cpu / _SPLIT_KEY1).
+// stream's own default second key word instead, so the data generator, the
+// train/test split and the cross-validation folds never draw from the same
+// stream for one seed (ops/reference.py: datagen_cpu / _SPLIT_KEY1 /
+// _FOLD_KEY1).
 #define PHILOX_DATAGEN_KEY1 0x1F123BB5u
 #define PHILOX_SPLIT_KEY1 0x85EBCA6Bu
 
@@ -79,6 +80,22 @@ static inline SplitKey split_key(int64_t seed, double test_frac) {
 __device__ __forceinline__ bool is_test_row(const SplitKey& k,
                                             unsigned long long i) {
   return philox4x32(i, k.key0, k.key1).x < k.tau;
+}
+
+// The cross-validation folds, a third stream: row i belongs to fold
+// (philox(key, i).x * folds) >> 32, in [0, folds)
+// (ops/reference.py: fold_ids_cpu / _FOLD_KEY1).
+#define PHILOX_FOLD_KEY1 0xC2B2AE35u
+
+static inline PhiloxKey fold_key(int64_t seed) {
+  return philox_key(seed, PHILOX_FOLD_KEY1);
+}
+
+__device__ __forceinline__ unsigned int fold_of_row(const PhiloxKey& k,
+                                                    unsigned long long i,
+                                                    unsigned int folds) {
+  return (unsigned int)(((unsigned long long)philox4x32(i, k.key0, k.key1).x *
+                         folds) >> 32);
 }
 
 // uniform in [0,1): u32 * 2^-32 (matches the numpy oracle's float32 math)

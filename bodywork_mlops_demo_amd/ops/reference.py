@@ -144,6 +144,47 @@ def poly_stats_cpu(X, y, nf: int, mu: float, s: float) -> torch.Tensor:
     return torch.tensor(out, dtype=torch.float64)
 
 
+_FOLD_KEY1 = 0xC2B2AE35  # the cross-validation folds' own philox stream
+
+POLY_FOLD_MAXDEG = 5
+POLY_FOLD_K = 3 * POLY_FOLD_MAXDEG + 3  # S_0..S_10, T_0..T_5, Q
+
+
+def fold_ids_cpu(n: int, folds: int, seed: int = 42) -> np.ndarray:
+    """Fold of every row 0..n-1 (int64): ``(philox(key, i).x * folds) >>
+    32`` — the rule of ``fold_of_row`` in ops/hip/philox.h."""
+    key1 = (seed >> 32) if seed > 0xFFFFFFFF else _FOLD_KEY1
+    r = philox4x32(np.arange(n, dtype=np.uint64), seed, key1)
+    return ((r[:, 0].astype(np.uint64) * np.uint64(folds))
+            >> np.uint64(32)).astype(np.int64)
+
+
+def poly_fold_stats_cpu(X, y, folds: int, seed: int, mu: float,
+                        s: float) -> torch.Tensor:
+    """CPU oracle of the poly_fold_stats kernel: fp64 ``[folds, 18]``, row
+    f = ``[S_0..S_10, T_0..T_5, Q]`` over the rows of fold f, with ``S_p =
+    sum t^p``, ``T_q = sum y t^q``, ``Q = sum y^2`` and t as in
+    :func:`poly_stats_cpu`."""
+    n = X.numel()
+    ids = fold_ids_cpu(n, folds, seed)
+    t = ((X.float() - np.float32(mu)) * np.float32(1.0 / s)) \
+        .numpy().astype(np.float64)
+    y64 = y.double().numpy()
+    ns = 2 * POLY_FOLD_MAXDEG + 1
+    out = np.zeros((folds, POLY_FOLD_K))
+    step = 1 << 18  # bounds the [rows, 18] feature block
+    for lo in range(0, n, step):
+        tc, yc = t[lo:lo + step], y64[lo:lo + step]
+        v = np.vander(tc, ns, increasing=True)  # repeated multiplication
+        feats = np.concatenate(
+            [v, yc[:, None] * v[:, :POLY_FOLD_MAXDEG + 1],
+             (yc * yc)[:, None]], axis=1)
+        onehot = (ids[lo:lo + step][None, :]
+                  == np.arange(folds)[:, None]).astype(np.float64)
+        out += onehot @ feats
+    return torch.from_numpy(out)
+
+
 def poly_score_cpu(X, coef, mu: float, s: float) -> torch.Tensor:
     if torch.is_tensor(coef):
         coef = coef.cpu().tolist()

@@ -172,7 +172,8 @@ def main(argv=None) -> None:
     p.add_argument("--days", type=int, default=30)
     p.add_argument("--rows", type=int, default=24 * 60)
     p.add_argument("--model", default="linear",
-                   help="linear | poly[<degree>] | mlp | mlp-fp8 "
+                   help="linear | poly[<degree>] | polycv[<max degree>] "
+                        "(degree and l2 by 5-fold CV) | mlp | mlp-fp8 "
                         "(mlp with the MX-fp8 scoring forward) | "
                         "mlp-fp8-train (mlp-fp8 plus the MX-fp8 training "
                         "forward) | mlp-fp8-train-bwd (mlp-fp8-train plus "

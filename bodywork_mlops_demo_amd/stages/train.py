@@ -22,6 +22,7 @@ from bodywork_mlops_demo_amd.models import (
     GPULinearRegressor,
     GPUMLPRegressor,
     GPUPolyRegressor,
+    GPUPolyRegressorCV,
 )
 from bodywork_mlops_demo_amd.monitoring import stage_guard
 from bodywork_mlops_demo_amd.store import ArtefactStore, contract, open_store
@@ -84,6 +85,13 @@ def run(
         model = GPULinearRegressor(device=device)
         metrics = model.fit_split(X, y, 0.2, seed=42,
                                   process_group=process_group)
+    elif model_type.startswith("polycv"):
+        # "polycv" (degrees 1..5) or "polycv<d>" (degrees 1..d): degree
+        # and l2 chosen by K-fold CV from one fold-statistics pass
+        max_degree = int(model_type[6:]) if len(model_type) > 6 else 5
+        model = GPUPolyRegressorCV(max_degree=max_degree, device=device).fit(
+            X_train, y_train, process_group=process_group
+        )
     elif model_type.startswith("poly"):
         # "poly" (degree 3) or "poly<d>", e.g. "poly2"
         degree = int(model_type[4:]) if len(model_type) > 4 else 3
@@ -124,12 +132,14 @@ def run(
         model_key = store.put_model(model.to_sklearn(), data_date)
         log.info(f"uploaded model to {model_key}")
         metrics_key = contract.model_metrics_key(data_date)
-        store.put_metrics_csv(
-            metrics_key,
-            ["date", "MAPE", "r_squared", "max_residual"],
-            [data_date, metrics["MAPE"], metrics["r_squared"],
-             metrics["max_residual"]],
-        )
+        header = ["date", "MAPE", "r_squared", "max_residual"]
+        row = [data_date, metrics["MAPE"], metrics["r_squared"],
+               metrics["max_residual"]]
+        if isinstance(model, GPUPolyRegressorCV):
+            # what the cross-validation chose; this model type only
+            header += ["cv_degree", "cv_l2", "cv_mse", "cv_folds"]
+            row += [model.degree, model.l2, model.best_score_, model.folds]
+        store.put_metrics_csv(metrics_key, header, row)
         log.info(f"uploaded metrics to {metrics_key}")
     if return_model:
         return metrics, model
@@ -140,7 +150,8 @@ def main(argv=None) -> None:
     p = argparse.ArgumentParser(description=__doc__)
     p.add_argument("--store", default=None, help="store URI (dir or s3://bucket)")
     p.add_argument("--model", default="linear",
-                   help="linear | poly[<degree>] | mlp")
+                   help="linear | poly[<degree>] | polycv[<max degree>] "
+                        "(degree and l2 by 5-fold CV) | mlp")
     p.add_argument("--device", default=None)
     p.add_argument("--mlp-steps", type=int, default=50)
     args = p.parse_args(argv)
