@@ -40,11 +40,12 @@ import torch
 from bodywork_mlops_demo_amd.ops import reference
 
 _HIPCORE = None
+_HIPMOD = None  # the same library as a Python module (its bound classes)
 _HIPCORE_ERR: str | None = None
 
 
 def _load_extension():
-    global _HIPCORE, _HIPCORE_ERR
+    global _HIPCORE, _HIPMOD, _HIPCORE_ERR
     if _HIPCORE is not None or _HIPCORE_ERR is not None:
         return _HIPCORE
     here = os.path.dirname(__file__)
@@ -58,6 +59,9 @@ def _load_extension():
         return None
     try:
         torch.ops.load_library(cands[0])
+        import importlib
+
+        _HIPMOD = importlib.import_module(__name__ + "._hipcore")
         _HIPCORE = torch.ops.bodywork_hip
     except Exception as e:  # loud: a broken build must not silently fall back
         _HIPCORE_ERR = f"failed to load {cands[0]}: {e}"
@@ -84,6 +88,33 @@ def _core(device: torch.device):
             + str(_HIPCORE_ERR)
         )
     return ext
+
+
+# --------------------------------------------------------------------------
+# native artefact writer — ops/hip/artefact_writer.cpp, artefact_stage.cpp
+# --------------------------------------------------------------------------
+
+def _hipmod():
+    if _load_extension() is None:
+        raise RuntimeError(
+            "the _hipcore HIP extension is not built: " + str(_HIPCORE_ERR))
+    return _HIPMOD
+
+
+def npy_header(n: int) -> bytes:
+    """The header bytes ``np.save`` writes for a 1-D little-endian float32
+    array of ``n`` elements, as the native writer builds them."""
+    return _hipmod().npy_header(int(n))
+
+
+def dataset_persister(workers: int, slots: int):
+    """A native ``DatasetPersister``: ``submit(y, X, path)`` stages a day's
+    1-D float32 CUDA tensors as one complete ``.npy``-pair file image in a
+    ring of ``slots`` pinned buffers (D2H on a side stream) and ``workers``
+    GIL-free threads write ``<dir>/.tmp-*`` and rename it to ``path``.
+    ``submit`` returns a handle with ``done()`` / ``result()``; ``drain()``
+    waits for everything and raises the first write error."""
+    return _hipmod().DatasetPersister(int(workers), int(slots))
 
 
 # --------------------------------------------------------------------------

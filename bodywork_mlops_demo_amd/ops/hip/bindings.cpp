@@ -102,6 +102,8 @@ at::Tensor batch_indices_hip(at::Tensor ctr, const at::Tensor& n_dev,
                              int64_t bs, int64_t seed);
 at::Tensor transpose_to_bf16_hip(const at::Tensor& src);
 at::Tensor transpose_bf16_hip(const at::Tensor& src);
+// artefact_stage.cpp -- classes, so bound on the Python module itself
+void bind_artefact_stage(pybind11::module_& m);
 
 TORCH_LIBRARY(bodywork_hip, m) {
   m.def("datagen(int n, int seed, int stream_offset, float alpha, float beta, "
@@ -211,4 +213,5 @@ TORCH_LIBRARY_IMPL(bodywork_hip, CompositeExplicitAutograd, m) {
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "bodywork_mlops_demo_amd gfx950 HIP kernels";
+  bind_artefact_stage(m);
 }

@@ -135,16 +135,24 @@ class CycleState:
         bench (any rank's shard is an equally representative artefact)."""
         return self.cycle_count % max(self.world_size, 1)
 
-    # -- async artefact I/O: dataset D2H copies run on a side stream
-    #    through a ring of pinned staging pairs and the file writes run
-    #    on I/O threads after the copy event fires, overlapping the
-    #    next stages' compute.  Consecutive days are separate files, so
-    #    two writes are in flight at once (a single writer copying into
-    #    the page cache was the longest serial chain of a 10M-row cycle).
-    #    drain_io() before reading artefacts back or stopping a
-    #    benchmark clock.
-    IO_WORKERS = 2
-    PIN_SLOTS = 3  # one being filled + one per writer
+    # -- async artefact I/O: a day's dataset goes to its file without
+    #    blocking the pipeline.  For CUDA tensors and a LocalStore the
+    #    whole chain is native (ops.dataset_persister): the D2H copies run
+    #    on a side stream straight into a complete file image in a ring
+    #    of PIN_SLOTS pinned buffers, and IO_WORKERS C++ threads wait for
+    #    the copy event, write a temporary file and rename it -- no
+    #    Python, so no GIL hand-off, between copy and rename.  Consecutive
+    #    days are separate files, so several writes are in flight at once
+    #    (parallelism stays across files: writers of one file serialise
+    #    on its inode lock).  One 74 MB day takes a writer 6-7.5 ms of
+    #    page-cache copy on the MI355X hosts, so four writers keep up
+    #    with a 2 ms cycle and the slot wait disappears; two or three do
+    #    not (profiles/native_artefact_writer.md).  Every other case (CPU tensors, CSV, other
+    #    stores) goes through a Python thread pool of the same size and
+    #    store.put_dataset.  drain_io() before reading artefacts back or
+    #    stopping a benchmark clock.
+    IO_WORKERS = 4  # measured; a DP node runs one persister per rank
+    PIN_SLOTS = IO_WORKERS + 1  # one being filled + one per writer
 
     def submit_io(self, fn, *args):
         if self._io_pool is None:
@@ -156,9 +164,13 @@ class CycleState:
         return fut
 
     def drain_io(self) -> None:
-        for f in self._io_futures:
-            f.result()  # re-raises write errors
-        self._io_futures.clear()
+        try:
+            for f in self._io_futures:
+                f.result()  # re-raises write errors
+        finally:
+            self._io_futures.clear()
+            if getattr(self, "_persister", None) is not None:
+                self._persister.drain()  # re-raises write errors too
 
     def _pin_view(self, name: str, numel: int, dtype) -> torch.Tensor:
         if getattr(self, "_pin", None) is None:
@@ -172,12 +184,29 @@ class CycleState:
     def persist_async(self, store, d, y: torch.Tensor, X: torch.Tensor,
                       fmt: str) -> None:
         """Persist a day's dataset without blocking the pipeline: the D2H
-        copies run on a side stream through cached pinned buffers
-        (overlapping the next stage's compute) and the file write runs on
-        an I/O thread after the copy event fires.  A pinned pair is
-        reused only after the write that last used it has finished."""
+        copies run on a side stream into pinned staging memory
+        (overlapping the next stage's compute) and the file is written on
+        an I/O thread after the copy event fires -- natively for a plain
+        LocalStore, through store.put_dataset otherwise.  A staging slot
+        is reused only after the write that last used it has finished."""
         if y.device.type != "cuda":
             self.submit_io(store.put_dataset, d, y.numpy(), X.numpy(), fmt)
+            return
+        if self._native_persist(store, y, X, fmt):
+            if getattr(self, "_persister", None) is None:
+                import weakref
+
+                self._persister = ops.dataset_persister(self.IO_WORKERS,
+                                                        self.PIN_SLOTS)
+                # join the writer threads before the interpreter goes away
+                weakref.finalize(self, self._persister.close)
+            if getattr(self, "_pin_futures", None) is None:
+                self._pin_futures = {}
+            slot = (getattr(self, "_pin_slot", -1) + 1) % self.PIN_SLOTS
+            # waits (GIL released) for the write that last used the slot
+            self._pin_futures[slot] = self._persister.submit(
+                y, X, store.dataset_path(d))
+            self._pin_slot = slot
             return
         # ring of pinned staging pairs, each guarded by the future of the
         # write that last used it (PIN_SLOTS persists ago): with two
@@ -212,6 +241,17 @@ class CycleState:
             store.put_dataset(d, yv.numpy(), Xv.numpy(), fmt)
 
         self._pin_futures[slot] = self.submit_io(_write)
+
+    @staticmethod
+    def _native_persist(store, y, X, fmt: str) -> bool:
+        """The native writer serves the binary dataset record of a plain
+        LocalStore (a subclass may have its own put_* methods)."""
+        from bodywork_mlops_demo_amd.store import LocalStore
+
+        return (type(store) is LocalStore and fmt in ("npy", "npz", "bin")
+                and ops.hip_available()
+                and all(t.is_cuda and t.dim() == 1 and t.is_contiguous()
+                        and t.dtype == torch.float32 for t in (y, X)))
 
     def append_day(self, y: torch.Tensor, X: torch.Tensor) -> None:
         add = int(y.shape[0])

@@ -75,6 +75,16 @@ class LocalStore(ArtefactStore):
                 os.unlink(tmp)
             raise
 
+    def dataset_path(self, d) -> str:
+        """Absolute path of day ``d``'s binary dataset artefact, its
+        directory created — for a writer that goes to the file directly
+        (tmp-file + rename in that directory, as :meth:`put_stream`)."""
+        from bodywork_mlops_demo_amd.store import contract
+
+        path = self._path(contract.dataset_key(d, "npy"))
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        return path
+
     def exists(self, key: str) -> bool:
         return os.path.isfile(self._path(key))
 

@@ -20,6 +20,8 @@ TORCH_LIB = os.path.join(os.path.dirname(torch.__file__), "lib")
 
 sources = [
     os.path.join(HIP_DIR, "bindings.cpp"),
+    os.path.join(HIP_DIR, "artefact_writer.cpp"),
+    os.path.join(HIP_DIR, "artefact_stage.cpp"),
     os.path.join(HIP_DIR, "datagen.hip"),
     os.path.join(HIP_DIR, "linreg.hip"),
     os.path.join(HIP_DIR, "drift_hist.hip"),
