@@ -18,10 +18,14 @@ import torch
 from bodywork_mlops_demo_amd.utils.device import canonical_device
 
 from bodywork_mlops_demo_amd import ops
+from bodywork_mlops_demo_amd.models import conformal
 
 
 class GPULinearRegressor:
     """y = intercept + coef * x, fit by fused-stats closed form."""
+
+    #: optional split-conformal calibration (models/conformal.py)
+    conformal_: "conformal.Calibration | None" = None
 
     def __init__(self, intercept: float = 0.0, coef: float = 0.0, device="cpu"):
         self.intercept_ = float(intercept)
@@ -47,6 +51,7 @@ class GPULinearRegressor:
         if not isinstance(other, GPULinearRegressor):
             return False
         self.intercept_, self.coef_ = other.intercept_, other.coef_
+        self.conformal_ = other.conformal_
         self._sync_ab()
         return True
 
@@ -116,7 +121,7 @@ class GPULinearRegressor:
         m.coef_ = np.array([self.coef_])
         m.intercept_ = float(self.intercept_)
         m.n_features_in_ = 1
-        return m
+        return conformal.attach(m, self.conformal_)
 
     @classmethod
     def from_sklearn(cls, m, device="cpu") -> "GPULinearRegressor":

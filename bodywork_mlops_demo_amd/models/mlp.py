@@ -38,6 +38,7 @@ import torch
 from bodywork_mlops_demo_amd.utils.device import canonical_device
 
 from bodywork_mlops_demo_amd import ops
+from bodywork_mlops_demo_amd.models import conformal
 from bodywork_mlops_demo_amd.utils.logging import configure_logger
 
 log = configure_logger(__name__)
@@ -55,6 +56,9 @@ class GPUMLPRegressor:
     #: data-free bound on |xn| for the reference's X ~ U(0,100)
     #: (stage_3:39): (100 - mu) / sigma ~= 1.74
     XN_BOUND = 1.8
+
+    #: optional split-conformal calibration (models/conformal.py)
+    conformal_: "conformal.Calibration | None" = None
 
     def __init__(self, hidden: int = 4096, device="cpu", seed: int = 7,
                  fp8_scoring: bool | None = None,
@@ -148,6 +152,7 @@ class GPUMLPRegressor:
             getattr(self, name).copy_(getattr(other, name).to(self.device))
         for name in ("w1_bf", "b1_bf", "W2w_bf", "W2wt_bf", "b2_bf", "w3_bf"):
             getattr(self, name).copy_(getattr(other, name).to(self.device))
+        self.conformal_ = other.conformal_
         self._refresh_fp8()
         self._refresh_fp8_train()
         return True
@@ -685,7 +690,7 @@ class GPUMLPRegressor:
         m.n_outputs_ = 1
         m.out_activation_ = "identity"
         m.n_features_in_ = 1
-        return m
+        return conformal.attach(m, self.conformal_)
 
     @classmethod
     def from_sklearn(cls, m, device="cpu") -> "GPUMLPRegressor":

@@ -26,11 +26,14 @@ import torch
 from bodywork_mlops_demo_amd.utils.device import canonical_device
 
 from bodywork_mlops_demo_amd import ops
+from bodywork_mlops_demo_amd.models import conformal
 
 
 class GPUPolyRegressor:
     X_MU = 50.0
     X_SIGMA = 50.0  # scale to t in [-1, 1] for U(0,100) inputs
+    #: optional split-conformal calibration (models/conformal.py)
+    conformal_: "conformal.Calibration | None" = None
 
     def __init__(self, degree: int = 3, l2: float = 1e-6, device="cpu"):
         if not 1 <= degree <= 5:
@@ -82,6 +85,7 @@ class GPUPolyRegressor:
             return False
         self.coef_t_ = list(other.coef_t_)
         self.l2 = other.l2
+        self.conformal_ = other.conformal_
         self._sync_dev()
         return True
 
@@ -123,7 +127,8 @@ class GPUPolyRegressor:
         ridge.coef_ = raw[1:].copy()
         ridge.intercept_ = float(raw[0])
         ridge.n_features_in_ = self.degree
-        return Pipeline([("poly", poly), ("ridge", ridge)])
+        return conformal.attach(Pipeline([("poly", poly), ("ridge", ridge)]),
+                                self.conformal_)
 
     @classmethod
     def from_sklearn(cls, pipe, device="cpu") -> "GPUPolyRegressor":

@@ -66,7 +66,38 @@ def drift_report(store: ArtefactStore) -> dict:
                 max_ks_residual=float(joined["ks_residual"].max()),
                 days_drifted=int(joined["drifted"].fillna(0).sum()),
             )
+        coverage = coverage_history(online)
+        if coverage:
+            # the conformal-interval check's columns (stages/loadtest.py)
+            report["coverage"] = coverage
+            report["summary"].update({
+                f"pi{pct}_{k}": c[k] for pct, c in coverage.items()
+                for k in ("mean_coverage", "min_coverage", "days_below")})
     return report
+
+
+def coverage_history(online: pd.DataFrame) -> dict:
+    """Per calibrated level ``<pct>`` (from the ``pi<pct>_coverage`` columns
+    of the test-metrics history): the coverage per day and its summary.
+    Days without the columns are left out."""
+    out = {}
+    for col in online.columns:
+        if not (col.startswith("pi") and col.endswith("_coverage")):
+            continue
+        pct = col[2:-len("_coverage")]
+        days = online[["date", col]].dropna()
+        if days.empty:
+            continue
+        ok = online.get(f"pi{pct}_ok")
+        out[pct] = {
+            "per_day": [(str(d.date()), float(c))
+                        for d, c in zip(days["date"], days[col])],
+            "mean_coverage": float(days[col].mean()),
+            "min_coverage": float(days[col].min()),
+            "days_below": int((ok.dropna() == 0).sum()) if ok is not None
+            else 0,
+        }
+    return out
 
 
 def plot_drift(report: dict, path: str) -> str:
@@ -122,6 +153,10 @@ def main(argv=None) -> None:
         pd.set_option("display.width", 160)
         print(report["joined"].to_string(index=False))
         print("\nsummary:", report["summary"])
+        for pct, c in report.get("coverage", {}).items():
+            print(f"\ncoverage of the {pct}% prediction intervals per day:")
+            for day, cov in c["per_day"]:
+                print(f"  {day}  {cov:.4f}")
         if args.csv_out:
             report["joined"].to_csv(args.csv_out, index=False)
         if args.plot:

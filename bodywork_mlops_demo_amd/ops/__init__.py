@@ -19,6 +19,11 @@ here every computational primitive is a first-class gfx950 kernel
 - ``drift_histograms`` — fused histograms of features, labels, scores and
                        residuals for the drift monitor (no reference
                        counterpart)
+- ``residual_quantiles`` — exact order statistics of |label - score| by a
+                       three-pass device radix select, the half-widths of
+                       split-conformal prediction intervals; and
+                       ``interval_coverage``, the rows inside such bands
+                       (no reference counterpart)
 - ``gemm_bf16``      — MFMA (v_mfma_f32_16x16x32_bf16) LDS-tiled dense
                        GEMM with fused bias+ReLU epilogue for the MLP path
 
@@ -530,6 +535,151 @@ def drift_histograms(
             scores.contiguous().float(), int(spec.bins), lo, scale)
     return reference.drift_histograms_cpu(X, labels, scores, int(spec.bins),
                                           lo, scale)
+
+
+# --------------------------------------------------------------------------
+# conformal intervals — exact residual order statistics and band coverage
+# --------------------------------------------------------------------------
+
+#: levels per call (one LDS table per level in the later select passes)
+MAX_CONFORMAL_LEVELS = 4
+_RESID_SELECT_PASSES = 3   # RS_PASSES in ops/hip/resid_select.h
+_RESID_SELECT_STATE = 14   # RS_STATE
+
+
+def check_levels(levels) -> tuple[float, ...]:
+    """``levels`` as a tuple of 1..4 floats, each in (0, 1); ValueError
+    otherwise."""
+    try:
+        lv = tuple(float(v) for v in levels)
+    except TypeError:
+        lv = (float(levels),)
+    if not 1 <= len(lv) <= MAX_CONFORMAL_LEVELS:
+        raise ValueError(
+            f"conformal levels: between 1 and {MAX_CONFORMAL_LEVELS} levels "
+            f"(got {len(lv)})")
+    for v in lv:
+        if not 0.0 < v < 1.0:
+            raise ValueError(f"conformal levels lie in (0, 1) (got {v})")
+    return lv
+
+
+def allreduce_counts(t: torch.Tensor, process_group) -> torch.Tensor:
+    """SUM ``t`` over the group (through host memory unless the backend is
+    nccl, as the drift monitor does) and hand it back on its device."""
+    import torch.distributed as dist
+
+    if t.device.type == "cuda" and dist.get_backend(process_group) != "nccl":
+        h = t.cpu()
+        dist.all_reduce(h, op=dist.ReduceOp.SUM, group=process_group)
+        return h.to(t.device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=process_group)
+    return t
+
+
+def _resid_select(a, b, levels, process_group, ab=None, test_frac=0.0,
+                  seed=0):
+    """The device select: per pass one histogram sweep, an optional
+    all-reduce of the histogram (histograms of row shards add) and the
+    one-block pick.  Nothing is read back before the last pick."""
+    core = _core(a.device)
+    state = torch.zeros(_RESID_SELECT_STATE, dtype=torch.int64,
+                        device=a.device)
+    hw = None
+    for p in range(_RESID_SELECT_PASSES):
+        hist = core.resid_select_pass(a, b, state, p, len(levels), ab,
+                                      float(test_frac), int(seed))
+        if process_group is not None:
+            hist = allreduce_counts(hist, process_group)
+        hw = core.resid_select_pick(hist, state, p, list(levels))
+    m, n_nan = state[:2].tolist()
+    return hw, int(m), int(n_nan)
+
+
+def _select_cpu(r: np.ndarray, levels, process_group):
+    if process_group is not None:
+        import torch.distributed as dist
+
+        parts = [None] * dist.get_world_size(process_group)
+        dist.all_gather_object(parts, r, group=process_group)
+        r = np.concatenate(parts)
+    return reference.select_residuals_cpu(r, levels)
+
+
+def residual_quantiles(
+    labels: torch.Tensor, scores: torch.Tensor, levels, process_group=None
+) -> tuple[torch.Tensor, int, int]:
+    """Split-conformal half-widths: exact order statistics of
+    ``|labels - scores|``.
+
+    Returns ``(halfwidths, m, n_nan)``: ``halfwidths`` is fp32 ``[Q]`` on
+    the inputs' device, ``m`` the number of non-NaN residuals, ``n_nan``
+    the number left out as NaN.  Level L gets the k-th smallest residual,
+    ``k = ceil((m + 1) * L)``, or +inf when ``k > m`` — so a fresh
+    exchangeable row lies within ``prediction ± halfwidth`` with
+    probability at least L.  On the GPU this is a three-pass radix select
+    (``ops/hip/resid_select.h``): no sort, and one host read at the end.
+    With a ``process_group`` every rank passes its row shard, the pass
+    histograms are all-reduced and every rank gets the quantiles of the
+    union.  Up to four levels, each in (0, 1).
+    """
+    levels = check_levels(levels)
+    if labels.device.type == "cuda":
+        return _resid_select(labels.contiguous().float(),
+                             scores.contiguous().float(), levels,
+                             process_group)
+    return _select_cpu(reference.abs_residuals_cpu(labels, scores), levels,
+                       process_group)
+
+
+def linear_split_residual_quantiles(
+    X: torch.Tensor,
+    y: torch.Tensor,
+    ab,
+    levels,
+    test_frac: float = 0.2,
+    seed: int = 42,
+    process_group=None,
+) -> tuple[torch.Tensor, int, int]:
+    """:func:`residual_quantiles` of the linear model ``ab = [intercept,
+    coef]`` over the TEST rows of ``random_split(X, y, test_frac, seed)``,
+    without materialising split or predictions: the philox flag and the
+    score are evaluated inside the select passes."""
+    levels = check_levels(levels)
+    if X.device.type == "cuda":
+        if not torch.is_tensor(ab):
+            ab = torch.tensor([float(ab[0]), float(ab[1])])
+        return _resid_select(
+            y.contiguous().float(), X.contiguous().float(), levels,
+            process_group, ab=ab.to(X.device, torch.float32).contiguous(),
+            test_frac=test_frac, seed=seed)
+    _, _, X_te, y_te = reference.random_split_cpu(X, y, test_frac, seed)
+    yhat = reference.linear_score_cpu(X_te, float(ab[0]), float(ab[1]))
+    return _select_cpu(reference.abs_residuals_cpu(y_te, yhat), levels,
+                       process_group)
+
+
+def interval_coverage(
+    scores: torch.Tensor, labels: torch.Tensor, halfwidths
+) -> torch.Tensor:
+    """How many rows lie inside each constant band: float64 ``[n, c_0 ..
+    c_3]`` on the inputs' device, ``c_q`` the count of rows with ``|label -
+    score| <= halfwidths[q]`` — exact integers, one fused 8 B/row pass.
+    ``halfwidths`` holds up to four fp32 values (a tensor or floats);
+    missing ones are padded with -1 and count nothing, as does a NaN
+    residual."""
+    h = torch.as_tensor(halfwidths, dtype=torch.float32).reshape(-1)
+    if h.numel() > MAX_CONFORMAL_LEVELS:
+        raise ValueError(
+            f"interval_coverage: at most {MAX_CONFORMAL_LEVELS} half-widths")
+    pad = h.new_full((MAX_CONFORMAL_LEVELS - h.numel(),), -1.0)
+    h = torch.cat([h, pad])
+    if scores.device.type == "cuda":
+        core = _core(scores.device)
+        return core.interval_coverage(scores.contiguous().float(),
+                                      labels.contiguous().float(),
+                                      h.to(scores.device))
+    return reference.interval_coverage_cpu(scores, labels, h)
 
 
 # --------------------------------------------------------------------------

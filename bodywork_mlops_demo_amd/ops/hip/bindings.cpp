@@ -30,11 +30,21 @@ at::Tensor linear_split_metrics_hip(const at::Tensor& x, const at::Tensor& y,
                                     const at::Tensor& ab, double test_frac,
                                     int64_t seed);
 at::Tensor score_label_metrics_hip(const at::Tensor& s, const at::Tensor& l);
+at::Tensor interval_coverage_hip(const at::Tensor& s, const at::Tensor& l,
+                                 const at::Tensor& halfwidths);
 // drift_hist.hip
 at::Tensor drift_histograms_hip(const at::Tensor& x, const at::Tensor& labels,
                                 const at::Tensor& scores, int64_t bins,
                                 at::ArrayRef<double> lo,
                                 at::ArrayRef<double> scale);
+// resid_select.hip
+at::Tensor resid_select_pass_hip(const at::Tensor& a, const at::Tensor& b,
+                                 const at::Tensor& state, int64_t pass,
+                                 int64_t nq,
+                                 const c10::optional<at::Tensor>& ab,
+                                 double test_frac, int64_t seed);
+at::Tensor resid_select_pick_hip(const at::Tensor& hist, at::Tensor state,
+                                 int64_t pass, at::ArrayRef<double> levels);
 // mlp_small.hip
 std::tuple<at::Tensor, at::Tensor> expand1d_bf16_hip(
     const at::Tensor& x, const at::Tensor& w,
@@ -125,6 +135,11 @@ TORCH_LIBRARY(bodywork_hip, m) {
   m.def("score_label_metrics(Tensor s, Tensor l) -> Tensor");
   m.def("drift_histograms(Tensor x, Tensor labels, Tensor scores, int bins, "
         "float[] lo, float[] scale) -> Tensor");
+  m.def("interval_coverage(Tensor s, Tensor l, Tensor halfwidths) -> Tensor");
+  m.def("resid_select_pass(Tensor a, Tensor b, Tensor state, int pass_index, "
+        "int nq, Tensor? ab, float test_frac, int seed) -> Tensor");
+  m.def("resid_select_pick(Tensor hist, Tensor(a!) state, int pass_index, "
+        "float[] levels) -> Tensor");
   m.def("expand1d_bf16(Tensor x, Tensor w, Tensor? b, bool relu, "
         "Tensor? mask, bool emit_mask, Tensor? n_dev) -> (Tensor, Tensor)");
   m.def("rowdot_bf16(Tensor h, Tensor w, Tensor bias) -> Tensor");
@@ -179,6 +194,9 @@ TORCH_LIBRARY_IMPL(bodywork_hip, CUDA, m) {
   m.impl("regression_metrics", regression_metrics_hip);
   m.impl("score_label_metrics", score_label_metrics_hip);
   m.impl("drift_histograms", drift_histograms_hip);
+  m.impl("interval_coverage", interval_coverage_hip);
+  m.impl("resid_select_pass", resid_select_pass_hip);
+  m.impl("resid_select_pick", resid_select_pick_hip);
   m.impl("expand1d_bf16", expand1d_bf16_hip);
   m.impl("rowdot_bf16", rowdot_bf16_hip);
   m.impl("coldot_bf16", coldot_bf16_hip);

@@ -10,6 +10,8 @@
 //                     grid-stride (hipGraph-capturable: no allocs/syncs).
 //   - regression_metrics / score_label_metrics: one fused pass producing
 //     every sum the MAPE/R^2/max-residual/Pearson formulas need.
+//   - interval_coverage: how many rows fall inside up to four constant
+//     prediction bands, as one more statistic of the same skeleton.
 //   - linreg_split_stats / linear_split_metrics: the same two passes with
 //     the philox train/test flag of random_split evaluated in-kernel, so
 //     the linear fit never materialises the split.
@@ -555,4 +557,44 @@ at::Tensor score_label_metrics_hip(const at::Tensor& s, const at::Tensor& l) {
   auto sf = s.scalar_type() == at::kFloat ? s : s.to(at::kFloat);
   auto lf = l.scalar_type() == at::kFloat ? l : l.to(at::kFloat);
   return stream_reduce2(sf, lf, ScoreLabelSums{});
+}
+
+// ---- interval_coverage (conformal bands: |label - score| <= half-width) ----
+// out = [n, c0, c1, c2, c3]
+//
+// ws row = [c0..c3] over rows (score, label): c_q counts the rows with
+// fabsf(__fsub_rn(label, score)) <= h[q], the residual of resid_select.h's
+// key rule.  h is four fp32 half-widths in device memory; an unused level
+// is passed as -1 and never counts, a NaN residual never counts, and +inf
+// covers every other row.  The counts are exact integers in fp64.
+struct CoverageSums {
+  static constexpr int NSUM = 4;
+  static constexpr int MAX_POS = -1;
+  static constexpr bool COUNTS = false;
+  const float* hw;  // device fp32[4]
+  float h[NSUM];
+
+  __device__ void begin() {
+#pragma unroll
+    for (int q = 0; q < NSUM; ++q) h[q] = hw[q];
+  }
+  __device__ __forceinline__ void row(long long, float s, float l,
+                                      double (&sum)[NSUM], double&,
+                                      unsigned int&) const {
+    const float r = fabsf(__fsub_rn(l, s));
+#pragma unroll
+    for (int q = 0; q < NSUM; ++q) sum[q] += r <= h[q] ? 1.0 : 0.0;
+  }
+};
+
+at::Tensor interval_coverage_hip(const at::Tensor& s, const at::Tensor& l,
+                                 const at::Tensor& halfwidths) {
+  TORCH_CHECK(s.is_cuda() && l.is_cuda() && s.numel() == l.numel());
+  TORCH_CHECK(s.scalar_type() == at::kFloat && l.scalar_type() == at::kFloat &&
+              s.is_contiguous() && l.is_contiguous());
+  TORCH_CHECK(halfwidths.is_cuda() && halfwidths.scalar_type() == at::kFloat &&
+                  halfwidths.is_contiguous() && halfwidths.numel() == 4,
+              "interval_coverage: halfwidths is a float32[4] device tensor "
+              "(unused levels -1)");
+  return stream_reduce2(s, l, CoverageSums{halfwidths.data_ptr<float>()});
 }

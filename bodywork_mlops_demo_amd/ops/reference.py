@@ -265,6 +265,62 @@ def drift_histograms_cpu(x, labels, scores, bins: int, lo, scale) -> torch.Tenso
 
 
 # --------------------------------------------------------------------------
+# conformal intervals: exact residual order statistics and band coverage
+# --------------------------------------------------------------------------
+
+def _f32(v) -> np.ndarray:
+    if torch.is_tensor(v):
+        v = v.detach().cpu().numpy()
+    return np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
+
+
+def abs_residuals_cpu(labels, scores) -> np.ndarray:
+    """``|labels - scores|`` as numpy float32, one rounded subtraction then
+    abs: the residual of the key rule in ``ops/hip/resid_select.h``."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        return np.abs(_f32(labels) - _f32(scores))
+
+
+def conformal_rank(m: int, level: float) -> int:
+    """``ceil((m + 1) * level)`` in fp64, the two IEEE operations the pick
+    kernel performs.  A rank above ``m`` means +inf."""
+    return int(math.ceil(float(m + 1) * float(level)))
+
+
+def select_residuals_cpu(r: np.ndarray, levels):
+    """``(halfwidths fp32[Q], m, n_nan)`` from float32 absolute residuals:
+    NaN is left out and counted, the rest sorted, level L reads index
+    ``conformal_rank(m, L) - 1`` or is +inf when the rank exceeds ``m``."""
+    r = np.asarray(r, dtype=np.float32).reshape(-1)
+    nan = np.isnan(r)
+    v = np.sort(r[~nan])
+    m = int(v.size)
+    out = np.empty(len(levels), dtype=np.float32)
+    for q, level in enumerate(levels):
+        k = conformal_rank(m, level)
+        out[q] = np.float32(np.inf) if k > m else v[k - 1]
+    return torch.from_numpy(out), m, int(nan.sum())
+
+
+def residual_quantiles_cpu(labels, scores, levels):
+    """Oracle of ``ops/hip/resid_select.hip`` and the CPU path of
+    :func:`ops.residual_quantiles`."""
+    return select_residuals_cpu(abs_residuals_cpu(labels, scores), levels)
+
+
+def interval_coverage_cpu(scores, labels, halfwidths) -> torch.Tensor:
+    """float64 ``[n, c_0 .. c_3]``: ``c_q`` counts the rows with
+    ``|label - score| <= halfwidths[q]`` (plain ``<=`` on float32, so NaN
+    never counts and -1 counts nothing) — the oracle of ``CoverageSums``
+    in ``ops/hip/linreg.hip``.  ``halfwidths`` holds four values."""
+    r = abs_residuals_cpu(labels, scores)
+    h = _f32(halfwidths)
+    with np.errstate(invalid="ignore"):
+        counts = [float(np.count_nonzero(r <= h[q])) for q in range(4)]
+    return torch.tensor([float(r.size), *counts], dtype=torch.float64)
+
+
+# --------------------------------------------------------------------------
 # GEMM oracle
 # --------------------------------------------------------------------------
 

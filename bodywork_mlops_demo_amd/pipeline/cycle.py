@@ -304,6 +304,7 @@ def run_cycle(
     http_port: int = 5600,
     capture: dict | None = None,
     drift_monitor=None,
+    conformal_levels=None,
 ) -> dict:
     """Run one full cycle; returns per-phase timings + metrics.
 
@@ -330,6 +331,13 @@ def run_cycle(
     newest training day scored by the freshly trained model (inside
     ``train_s``), and stage 4 observes day t+1 against it: the statistics
     join ``online`` and the test-metrics CSV.
+
+    ``conformal_levels``: stage 1 calibrates prediction intervals at these
+    confidence levels on its hold-out (inside ``train_s``; ``offline``
+    gains ``conformal``, the :class:`models.conformal.Calibration`) and
+    stage 4 checks their coverage on day t+1 (``pi<pct>_*`` in ``online``
+    and the test-metrics CSV).  A ``skip_train`` cycle checks the deployed
+    model's calibration.
     """
     device = state.device
     dev_cuda = device.startswith("cuda")
@@ -365,17 +373,18 @@ def run_cycle(
         timings["train_s"] = 0.0
         timings["deploy_s"] = 0.0
         metrics = scorer_cache.get("offline_metrics", {})
+        finish = dict(capture=capture, drift_monitor=drift_monitor,
+                      conformal=(scorer_cache.get("calibration")
+                                 if conformal_levels is not None else None),
+                      process_group=process_group)
         if serving == "http":
             replica = scorer_cache["http_replica"]
             return _finish_cycle(state, store, n_rows, persist_fmt, None,
                                  timings, metrics, sync,
-                                 http=(replica.url, http_mode),
-                                 capture=capture,
-                                 drift_monitor=drift_monitor)
+                                 http=(replica.url, http_mode), **finish)
         scorer = scorer_cache["scorer"]
         return _finish_cycle(state, store, n_rows, persist_fmt, scorer,
-                             timings, metrics, sync, capture=capture,
-                             drift_monitor=drift_monitor)
+                             timings, metrics, sync, **finish)
     metrics, trained = stage1.run(
         eff_store,
         model_type=model_type,
@@ -388,7 +397,15 @@ def run_cycle(
         data=(state.y, state.X, state.date),
         return_model=True,
         model_cache=scorer_cache,
+        conformal_levels=conformal_levels,
     )
+    finish = dict(capture=capture, drift_monitor=drift_monitor,
+                  conformal=None, process_group=process_group)
+    if conformal_levels is not None:
+        finish["conformal"] = trained.conformal_
+        metrics = dict(metrics, conformal=trained.conformal_)
+        if scorer_cache is not None:
+            scorer_cache["calibration"] = trained.conformal_
     if drift_monitor is not None:
         # reference distribution: the newest training day as the model
         # that was just fitted to it scores it
@@ -433,8 +450,7 @@ def run_cycle(
         timings["deploy_s"] = perf_counter() - t0
         return _finish_cycle(state, store, n_rows, persist_fmt, None,
                              timings, metrics, sync,
-                             http=(replica.url, http_mode), capture=capture,
-                             drift_monitor=drift_monitor)
+                             http=(replica.url, http_mode), **finish)
     if store is not None:
         if process_group is not None:  # rank 0 persisted; others wait
             import torch.distributed as dist
@@ -471,18 +487,20 @@ def run_cycle(
     timings["deploy_s"] = perf_counter() - t0
 
     return _finish_cycle(state, store, n_rows, persist_fmt, scorer, timings,
-                         metrics, sync, capture=capture,
-                         drift_monitor=drift_monitor)
+                         metrics, sync, **finish)
 
 
 def _finish_cycle(state, store, n_rows, persist_fmt, scorer, timings,
                   metrics, sync, http: tuple[str, str] | None = None,
-                  capture: dict | None = None, drift_monitor=None):
+                  capture: dict | None = None, drift_monitor=None,
+                  conformal=None, process_group=None):
     """Stages 3+4 and clock advance (shared by train and skip-train paths).
 
     ``http=(url, mode)`` routes stage 4 over the wire to a live replica
-    instead of the in-process scorer."""
+    instead of the in-process scorer.  ``conformal`` is the deployed
+    model's calibration, whose coverage stage 4 then checks."""
     device = state.device
+    extra = {"conformal": conformal, "process_group": process_group}
 
     # -- stage 3: generate day t+1 ------------------------------------------
     t0 = perf_counter()
@@ -508,6 +526,7 @@ def _finish_cycle(state, store, n_rows, persist_fmt, scorer, timings,
             persist=store is not None and state.rank == 0,
             capture=capture,
             drift_monitor=drift_monitor,
+            **extra,
         )
     else:
         test_metrics = stage4.run(
@@ -518,6 +537,7 @@ def _finish_cycle(state, store, n_rows, persist_fmt, scorer, timings,
             persist=store is not None and state.rank == 0,
             capture=capture,
             drift_monitor=drift_monitor,
+            **extra,
         )
     sync()
     timings["test_s"] = perf_counter() - t0

@@ -18,6 +18,7 @@ from datetime import date as date_t
 import torch
 
 from bodywork_mlops_demo_amd.pipeline.cycle import CycleState, run_cycle
+from bodywork_mlops_demo_amd.stages.train import parse_levels
 from bodywork_mlops_demo_amd.store import ArtefactStore, contract, open_store
 from bodywork_mlops_demo_amd.utils.logging import configure_logger
 
@@ -41,6 +42,7 @@ def run_loop(
     drift_monitor: bool = False,
     ks_alpha: float = 1e-3,
     ks_threshold: float | None = None,
+    conformal_levels=None,
 ) -> list[dict]:
     """Run ``days`` cycles.
 
@@ -59,6 +61,12 @@ def run_loop(
     ``drift_monitor`` adds the monitor's statistics
     (:mod:`monitoring.drift`) to every cycle's ``online`` dict and
     test-metrics CSV row without changing the policy.
+
+    ``conformal_levels`` (up to four confidence levels): every training
+    calibrates split-conformal prediction intervals and every day checks
+    their coverage on the unseen data (``pi<pct>_coverage`` /
+    ``_halfwidth`` / ``_ok`` in ``online`` and the test-metrics CSV).  A
+    calibration check, not a retrain policy.
     """
     device = device or ("cuda" if torch.cuda.is_available() else "cpu")
     if isinstance(start_date, str):
@@ -111,6 +119,7 @@ def run_loop(
             process_group=process_group, persist_fmt=persist_fmt,
             scorer_cache=scorer_cache, skip_train=skip,
             drift_monitor=monitor,
+            conformal_levels=conformal_levels,
         )
         results.append(r)
         if retrain_policy == "ks":
@@ -193,6 +202,11 @@ def main(argv=None) -> None:
     p.add_argument("--ks-threshold", type=float, default=None,
                    help="additional floor on the KS distance that counts "
                         "as drift")
+    p.add_argument("--conformal", default=None, type=parse_levels,
+                   metavar="LEVELS",
+                   help="calibrate prediction intervals at these confidence "
+                        "levels at every training and check their coverage "
+                        "every day, e.g. 0.9,0.95 (at most 4)")
     args = p.parse_args(argv)
     # env flags so the models built inside the cycle opt in
     args.model, env = resolve_model(args.model)
@@ -207,7 +221,7 @@ def main(argv=None) -> None:
         retrain_policy=args.retrain_policy,
         drift_threshold=args.drift_threshold,
         drift_monitor=args.drift_monitor, ks_alpha=args.ks_alpha,
-        ks_threshold=args.ks_threshold,
+        ks_threshold=args.ks_threshold, conformal_levels=args.conformal,
     )
     if args.json_out:
         with open(args.json_out, "w") as f:

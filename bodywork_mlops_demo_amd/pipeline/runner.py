@@ -475,7 +475,17 @@ def main(argv=None) -> None:
                         "pipeline date between runs")
     p.add_argument("--interval", type=float, default=0.0,
                    help="seconds to sleep between repeated runs")
+    p.add_argument("--conformal", default=None, metavar="LEVELS",
+                   help="prediction-interval confidence levels, e.g. "
+                        "0.9,0.95: the train stage calibrates them and the "
+                        "load-test stage checks their coverage (handed to "
+                        "the stages as BODYWORK_AMD_CONFORMAL)")
     args = p.parse_args(argv)
+    if args.conformal:
+        from bodywork_mlops_demo_amd.stages.train import parse_levels
+
+        parse_levels(args.conformal)  # fail here, not in a stage
+        os.environ["BODYWORK_AMD_CONFORMAL"] = args.conformal
     runner = PipelineRunner(args.config, store_uri=args.store,
                             secrets_file=args.secrets,
                             isolate_envs=args.isolate_envs)

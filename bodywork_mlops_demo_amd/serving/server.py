@@ -10,7 +10,18 @@ Extensions beyond the reference (batched GPU serving):
 - ``POST /score/v1/batch`` with ``{"X": [...]}`` returns
   ``{"predictions": [...], "n": n, "model_info": ...}``;
 - ``GET /healthz`` for the pipeline runner's startup probe (replaces the
-  k8s readiness mechanism implied by ``bodywork.yaml:39``).
+  k8s readiness mechanism implied by ``bodywork.yaml:39``);
+- prediction intervals, when the model artefact carries a split-conformal
+  calibration (``models/conformal.py``): an optional ``"confidence":
+  <level>`` in a ``/score/v1`` or ``/score/v1/batch`` request adds
+  ``"interval": [lo, hi]`` (a list of pairs for list input) and
+  ``"confidence"`` to the response, HTTP 422 naming the available levels
+  when there is no such calibration; ``/score/v1/binary`` sends the
+  levels and half-widths as ``X-Interval-Levels`` /
+  ``X-Interval-Halfwidths`` headers (the band is constant, the client
+  forms the intervals); ``/reload/v1`` and ``/healthz`` report the levels
+  as ``interval_levels``.  Requests without ``confidence`` to an
+  uncalibrated model get exactly the responses described above.
 
 Served by uvicorn (ASGI) instead of the reference's Flask dev server —
 one replica process per GPU, model resident in HBM, hipGraph-captured
@@ -25,6 +36,7 @@ not by intra-process concurrency.
 """
 from __future__ import annotations
 
+import math
 from contextlib import asynccontextmanager
 
 import numpy as np
@@ -40,48 +52,96 @@ from bodywork_mlops_demo_amd.utils.logging import configure_logger
 log = configure_logger(__name__)
 
 
+class _NoInterval(Exception):
+    """The request asked for a confidence the model cannot serve."""
+
+
+def _bound(v: float):
+    # JSON has no infinity: an unbounded side (a level whose rank exceeds
+    # the calibration set) is null
+    return v if math.isfinite(v) else None
+
+
 def create_app(store: ArtefactStore, device: str = "cpu",
                use_graphs: bool = True) -> FastAPI:
     state: dict = {}
     tracer = RequestTracer()
+
+    def set_model(model, model_date) -> None:
+        state["model_info"] = str(model)
+        state["model_date"] = str(model_date)
+        state["calibration"] = getattr(model, "conformal_", None)
+
+    def halfwidth(payload) -> tuple[float, float] | None:
+        """(level, half-width) for a request that carries ``confidence``."""
+        if "confidence" not in payload:
+            return None
+        cal = state.get("calibration")
+        try:
+            level = float(payload["confidence"])
+            if cal is None:
+                raise ValueError(
+                    f"no interval calibrated for confidence {level:g}; "
+                    "available levels: none (the model was trained without "
+                    "conformal calibration)")
+            return level, cal.halfwidth(level)
+        except (TypeError, ValueError) as e:
+            raise _NoInterval(str(e)) from e
+
+    def interval_fields(preds, hw, scalar: bool) -> dict:
+        level, h = hw
+        pairs = [[_bound(float(p) - h), _bound(float(p) + h)] for p in preds]
+        return {"interval": pairs[0] if scalar else pairs,
+                "confidence": level}
+
+    def levels_field() -> dict:
+        cal = state.get("calibration")
+        return {} if cal is None else {"interval_levels": list(cal.levels)}
 
     @asynccontextmanager
     async def lifespan(app: FastAPI):
         artefact, model_date = store.get_latest_model()
         model = regressor_from_artifact(artefact, device=device)
         state["scorer"] = BatchedScorer(model, device, use_graphs=use_graphs)
-        state["model_info"] = str(model)
-        state["model_date"] = str(model_date)
+        set_model(model, model_date)
         log.info(f"loaded model={state['model_info']} trained on {model_date} "
                  f"onto {device}")
         yield
 
     app = FastAPI(lifespan=lifespan)
 
+    @app.exception_handler(_NoInterval)
+    async def no_interval(request: Request, exc: _NoInterval) -> Response:
+        return JSONResponse({"detail": str(exc)}, status_code=422)
+
     @app.post("/score/v1")
     async def score_data_instance(request: Request) -> Response:
         payload = await request.json()
         features = payload["X"]
         scalar = np.isscalar(features)
+        hw = halfwidth(payload)
         with timed(tracer, rows=1 if scalar else len(features)):
             preds = state["scorer"].score(features)
         prediction = float(preds[0]) if scalar else [float(p) for p in preds]
-        return JSONResponse(
-            {"prediction": prediction, "model_info": state["model_info"]}
-        )
+        body = {"prediction": prediction, "model_info": state["model_info"]}
+        if hw is not None:
+            body.update(interval_fields(preds, hw, scalar))
+        return JSONResponse(body)
 
     @app.post("/score/v1/batch")
     async def score_batch(request: Request) -> Response:
         payload = await request.json()
+        hw = halfwidth(payload)
         with timed(tracer, rows=len(payload["X"])):
             preds = state["scorer"].score(payload["X"])
-        return JSONResponse(
-            {
-                "predictions": [float(p) for p in preds],
-                "n": int(preds.shape[0]),
-                "model_info": state["model_info"],
-            }
-        )
+        body = {
+            "predictions": [float(p) for p in preds],
+            "n": int(preds.shape[0]),
+            "model_info": state["model_info"],
+        }
+        if hw is not None:
+            body.update(interval_fields(preds, hw, scalar=False))
+        return JSONResponse(body)
 
     @app.post("/score/v1/binary")
     async def score_binary(request: Request) -> Response:
@@ -93,10 +153,17 @@ def create_app(store: ArtefactStore, device: str = "cpu",
         X = np.frombuffer(body, dtype=np.float32)
         with timed(tracer, rows=X.shape[0]):
             preds = state["scorer"].score(X)
+        headers = {"X-Model-Info": state["model_info"],
+                   "X-N": str(preds.shape[0])}
+        cal = state.get("calibration")
+        if cal is not None:
+            headers["X-Interval-Levels"] = ",".join(
+                repr(v) for v in cal.levels)
+            headers["X-Interval-Halfwidths"] = ",".join(
+                repr(v) for v in cal.halfwidths)
         return Response(content=preds.astype(np.float32).tobytes(),
                         media_type="application/octet-stream",
-                        headers={"X-Model-Info": state["model_info"],
-                                 "X-N": str(preds.shape[0])})
+                        headers=headers)
 
     @app.get("/stats")
     async def stats() -> Response:
@@ -128,13 +195,13 @@ def create_app(store: ArtefactStore, device: str = "cpu",
         if scorer is None or not scorer.update_model(model):
             state["scorer"] = BatchedScorer(model, device,
                                             use_graphs=use_graphs)
-        state["model_info"] = str(model)
-        state["model_date"] = str(model_date)
+        set_model(model, model_date)
         log.info(f"reloaded model={state['model_info']} trained on "
                  f"{model_date}")
         return JSONResponse({"status": "ok",
                              "model_date": state["model_date"],
-                             "model_info": state["model_info"]})
+                             "model_info": state["model_info"],
+                             **levels_field()})
 
     @app.get("/healthz")
     async def healthz() -> Response:
@@ -142,7 +209,8 @@ def create_app(store: ArtefactStore, device: str = "cpu",
         return JSONResponse(
             {"status": "ok" if ok else "starting",
              "model_date": state.get("model_date"),
-             "model_info": state.get("model_info")},
+             "model_info": state.get("model_info"),
+             **levels_field()},
             status_code=200 if ok else 503,
         )
 

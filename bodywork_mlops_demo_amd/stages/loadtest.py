@@ -141,6 +141,49 @@ def _score_binary(
     return scores, times
 
 
+#: one-sided 1e-3 normal quantile of the coverage check (the level of
+#: ``ks_alpha``'s default)
+COVERAGE_Z = 3.09
+
+
+def _calibration(conformal, store):
+    """``conformal`` as a Calibration: itself, or (``True``) the one on the
+    latest model artefact."""
+    from bodywork_mlops_demo_amd.models.conformal import Calibration, restore
+
+    if isinstance(conformal, Calibration):
+        return conformal
+    artefact, _ = store.get_latest_model()
+    cal = restore(artefact)
+    if cal is None:
+        raise ValueError("the latest model artefact carries no conformal "
+                         "calibration (train with conformal levels)")
+    return cal
+
+
+def coverage_metrics(cal, scores: torch.Tensor, labels: torch.Tensor,
+                     process_group=None) -> dict:
+    """``pi<pct>_coverage`` / ``_halfwidth`` / ``_ok`` per level of ``cal``,
+    in that order level by level, from one coverage pass."""
+    from bodywork_mlops_demo_amd.models.conformal import level_name
+
+    counts = ops.interval_coverage(scores, labels, cal.halfwidths)
+    if process_group is not None:
+        counts = ops.allreduce_counts(counts, process_group)
+    counts = counts.tolist()
+    n = counts[0]
+    out = {}
+    for q, (level, h) in enumerate(zip(cal.levels, cal.halfwidths)):
+        pct = level_name(level)
+        coverage = counts[1 + q] / n if n > 0 else float("nan")
+        floor = level - COVERAGE_Z * (level * (1.0 - level) / n) ** 0.5 \
+            if n > 0 else 0.0
+        out[f"pi{pct}_coverage"] = coverage
+        out[f"pi{pct}_halfwidth"] = h
+        out[f"pi{pct}_ok"] = 0 if coverage < floor else 1
+    return out
+
+
 def run(
     store: ArtefactStore,
     url: str = DEFAULT_URL,
@@ -151,6 +194,8 @@ def run(
     persist: bool = True,
     capture: dict | None = None,
     drift_monitor=None,
+    conformal=None,
+    process_group=None,
 ) -> dict:
     """Score the latest dataset against the service; persist test metrics.
 
@@ -159,6 +204,14 @@ def run(
     returned metrics and are appended as columns to the test-metrics CSV.
     Without one the metrics and the CSV are unchanged.
 
+    ``conformal`` (a :class:`models.conformal.Calibration`, or ``True``:
+    read it from the latest model artefact) checks the deployed model's
+    prediction intervals on the rows held here, in one
+    ``ops.interval_coverage`` pass: per level the metrics and the CSV gain
+    ``pi<pct>_coverage``, ``pi<pct>_halfwidth`` and ``pi<pct>_ok`` — 1
+    unless the coverage falls below ``level - z * sqrt(level * (1 - level)
+    / n)`` with z = 3.09, a one-sided 1e-3 binomial test.  These columns
+    come last.  With a ``process_group`` the counts are all-reduced.
 
     ``scorer`` bypasses HTTP entirely (in-process serving replica) for the
     hermetic pipeline/bench path; ``data`` skips the store read when the
@@ -217,6 +270,12 @@ def run(
 
         metrics.update(drift_monitor.observe(X.to(device), labels, scores))
         drift_keys = METRIC_KEYS
+    pi_keys: tuple = ()
+    if conformal:
+        cal = _calibration(conformal, store)
+        cov = coverage_metrics(cal, scores, labels, process_group)
+        metrics.update(cov)
+        pi_keys = tuple(cov)
     log.info(f"live-service metrics on {n} rows: {metrics}")
 
     if persist:
@@ -227,13 +286,15 @@ def run(
         store.put_metrics_csv(
             key,
             ["date", "MAPE", "r_squared", "max_residual",
-             "mean_response_time", "response_time_kind", *drift_keys],
+             "mean_response_time", "response_time_kind", *drift_keys,
+             *pi_keys],
             [data_date, metrics["MAPE"], metrics["r_squared"],
              metrics["max_residual"], metrics["mean_response_time"],
              rt_kind,
              # the decision as 0/1 so the analytics read it as a number
              *(int(metrics[k]) if k == "drifted" else metrics[k]
-               for k in drift_keys)],
+               for k in drift_keys),
+             *(metrics[k] for k in pi_keys)],
         )
         log.info(f"uploaded test metrics to {key}")
     return metrics
@@ -254,10 +315,15 @@ def main(argv=None) -> None:
     p.add_argument("--mode", default="batch",
                    choices=["serial", "batch", "binary"])
     p.add_argument("--device", default=None)
+    p.add_argument("--conformal", action="store_true",
+                   default=bool(os.environ.get("BODYWORK_AMD_CONFORMAL")),
+                   help="check the coverage of the prediction intervals the "
+                        "latest model artefact was calibrated for (default: "
+                        "on when $BODYWORK_AMD_CONFORMAL is set)")
     args = p.parse_args(argv)
     with stage_guard(STAGE_NAME, exit_on_error=True):
         run(open_store(args.store), url=args.url, mode=args.mode,
-            device=args.device)
+            device=args.device, conformal=args.conformal or None)
 
 
 if __name__ == "__main__":

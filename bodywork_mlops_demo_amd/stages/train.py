@@ -13,6 +13,7 @@ statistics/gradients.
 from __future__ import annotations
 
 import argparse
+import os
 from datetime import date as date_t
 
 import torch
@@ -24,6 +25,7 @@ from bodywork_mlops_demo_amd.models import (
     GPUPolyRegressor,
     GPUPolyRegressorCV,
 )
+from bodywork_mlops_demo_amd.models.conformal import Calibration, level_name
 from bodywork_mlops_demo_amd.monitoring import stage_guard
 from bodywork_mlops_demo_amd.store import ArtefactStore, contract, open_store
 from bodywork_mlops_demo_amd.utils.logging import configure_logger
@@ -49,6 +51,7 @@ def run(
     data: tuple[torch.Tensor, torch.Tensor, date_t] | None = None,
     return_model: bool = False,
     model_cache: dict | None = None,
+    conformal_levels=None,
 ):
     """Train and persist; returns the offline metrics record
     (or ``(metrics, model)`` when ``return_model``).
@@ -56,8 +59,16 @@ def run(
     ``data`` short-circuits store reads when the caller already holds the
     tensors in HBM (the in-process pipeline keeps data resident instead of
     re-reading artefacts — SURVEY.md §7 'keep tensors resident').
+
+    ``conformal_levels`` (up to four confidence levels in (0, 1)) calibrates
+    split-conformal prediction intervals on the 20 % hold-out: the
+    half-widths go onto the model (``conformal_``, and into its artefact)
+    and are appended to the model-metrics CSV as ``pi_cal_n`` and one
+    ``pi<pct>_halfwidth`` per level.  Without levels neither changes.
     """
     device = device or default_device()
+    levels = (ops.check_levels(conformal_levels)
+              if conformal_levels is not None else None)
     if data is None:
         y_np, X_np, data_date = store.get_all_datasets()
         X = torch.from_numpy(X_np).to(device)
@@ -123,10 +134,28 @@ def run(
     else:
         raise ValueError(f"unknown model_type {model_type!r}")
 
+    yhat = None
     if metrics is None:
         yhat = model.predict(X_test)
         metrics = ops.regression_metrics(y_test, yhat)
     log.info(f"offline metrics: {metrics}")
+
+    model.conformal_ = None
+    if levels is not None:
+        if model_type == "linear":
+            # the same never-materialised split as the fit: flag and score
+            # are evaluated inside the select passes
+            on_dev = X.device.type == "cuda" and model.device.type == "cuda"
+            ab = (model._ab_tensor() if on_dev
+                  else (model.intercept_, model.coef_))
+            selected = ops.linear_split_residual_quantiles(
+                X, y, ab, levels, 0.2, seed=42, process_group=process_group)
+        else:
+            selected = ops.residual_quantiles(
+                y_test, yhat, levels, process_group=process_group)
+        model.conformal_ = Calibration.from_select(levels, selected,
+                                                   date=data_date)
+        log.info(f"conformal calibration: {model.conformal_}")
 
     if rank == 0:
         model_key = store.put_model(model.to_sklearn(), data_date)
@@ -139,11 +168,24 @@ def run(
             # what the cross-validation chose; this model type only
             header += ["cv_degree", "cv_l2", "cv_mse", "cv_folds"]
             row += [model.degree, model.l2, model.best_score_, model.folds]
+        if model.conformal_ is not None:
+            cal = model.conformal_
+            header += ["pi_cal_n"] + [f"pi{level_name(lv)}_halfwidth"
+                                      for lv in cal.levels]
+            row += [cal.m, *cal.halfwidths]
         store.put_metrics_csv(metrics_key, header, row)
         log.info(f"uploaded metrics to {metrics_key}")
     if return_model:
         return metrics, model
     return metrics
+
+
+def parse_levels(text: str) -> tuple[float, ...]:
+    """``"0.9,0.95"`` -> ``(0.9, 0.95)`` for the ``--conformal`` options."""
+    try:
+        return ops.check_levels(float(v) for v in text.split(",") if v.strip())
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from e
 
 
 def main(argv=None) -> None:
@@ -154,10 +196,15 @@ def main(argv=None) -> None:
                         "(degree and l2 by 5-fold CV) | mlp")
     p.add_argument("--device", default=None)
     p.add_argument("--mlp-steps", type=int, default=50)
+    p.add_argument("--conformal", type=parse_levels, metavar="LEVELS",
+                   default=os.environ.get("BODYWORK_AMD_CONFORMAL") or None,
+                   help="calibrate prediction intervals at these confidence "
+                        "levels, e.g. 0.9,0.95 (at most 4, each in (0, 1)); "
+                        "default: $BODYWORK_AMD_CONFORMAL")
     args = p.parse_args(argv)
     with stage_guard(STAGE_NAME, exit_on_error=True):
         run(open_store(args.store), model_type=args.model, device=args.device,
-            mlp_steps=args.mlp_steps)
+            mlp_steps=args.mlp_steps, conformal_levels=args.conformal)
 
 
 if __name__ == "__main__":

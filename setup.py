@@ -25,6 +25,7 @@ sources = [
     os.path.join(HIP_DIR, "datagen.hip"),
     os.path.join(HIP_DIR, "linreg.hip"),
     os.path.join(HIP_DIR, "drift_hist.hip"),
+    os.path.join(HIP_DIR, "resid_select.hip"),
     os.path.join(HIP_DIR, "mlp_small.hip"),
     os.path.join(HIP_DIR, "gemm.hip"),
     os.path.join(HIP_DIR, "gemm8.hip"),
