@@ -24,6 +24,13 @@ here every computational primitive is a first-class gfx950 kernel
                        split-conformal prediction intervals; and
                        ``interval_coverage``, the rows inside such bands
                        (no reference counterpart)
+- ``binned_residual_quantiles`` — the same order statistics within each of
+                       up to 16 cells of X, all cells and levels in four
+                       shared passes (x-dependent, Mondrian conformal
+                       bands); ``linear_split_binned_residual_quantiles``
+                       on the never-materialised hold-out; and
+                       ``binned_interval_coverage``, per-cell coverage of
+                       such a band
 - ``gemm_bf16``      — MFMA (v_mfma_f32_16x16x32_bf16) LDS-tiled dense
                        GEMM with fused bias+ReLU epilogue for the MLP path
 
@@ -680,6 +687,142 @@ def interval_coverage(
                                       labels.contiguous().float(),
                                       h.to(scores.device))
     return reference.interval_coverage_cpu(scores, labels, h)
+
+
+# --------------------------------------------------------------------------
+# x-dependent (Mondrian) conformal intervals — one calibration per cell of X
+# --------------------------------------------------------------------------
+
+MAX_CONFORMAL_CELLS = 16            # BS_MAXC in ops/hip/resid_select_binned.h
+_BINNED_SELECT_PASSES = 4           # BS_PASSES
+
+
+def _cell_params(cells) -> tuple[int, float, float]:
+    """``cells.params()`` of a :class:`models.conformal.Cells`, the one
+    place the fp32 ``(n, lo, scale)`` of the cell rule is computed."""
+    n, lo, scale = cells.params()
+    if not 1 <= int(n) <= MAX_CONFORMAL_CELLS:
+        raise ValueError(
+            f"conformal cells: between 1 and {MAX_CONFORMAL_CELLS} (got {n})")
+    return int(n), float(lo), float(scale)
+
+
+def _binned_select(x, a, b, levels, cells, process_group, ab=None,
+                   test_frac=0.0, seed=0):
+    """The device select of every cell at once: per pass one histogram
+    sweep, an optional all-reduce of the histogram and the one-block-per-cell
+    pick.  Nothing is read back before the last pick."""
+    core = _core(x.device)
+    n, lo, scale = cells
+    state = torch.zeros((n, 2 + 3 * len(levels)), dtype=torch.int64,
+                        device=x.device)
+    hw = None
+    for p in range(_BINNED_SELECT_PASSES):
+        hist = core.resid_select_binned_pass(
+            x, a, b, state, p, len(levels), n, lo, scale, ab,
+            float(test_frac), int(seed))
+        if process_group is not None:
+            hist = allreduce_counts(hist, process_group)
+        hw = core.resid_select_binned_pick(hist, state, p, list(levels), n)
+    head = state[:, :2].cpu()
+    return hw, head[:, 0].contiguous(), int(head[0, 1])
+
+
+def _binned_select_cpu(cell, r, levels, n, process_group):
+    if process_group is not None:
+        import torch.distributed as dist
+
+        parts = [None] * dist.get_world_size(process_group)
+        dist.all_gather_object(parts, (cell, r), group=process_group)
+        cell = np.concatenate([p[0] for p in parts])
+        r = np.concatenate([p[1] for p in parts])
+    return reference.binned_select_residuals_cpu(cell, r, levels, n)
+
+
+def binned_residual_quantiles(
+    X: torch.Tensor, labels: torch.Tensor, scores: torch.Tensor, levels,
+    cells, process_group=None
+) -> tuple[torch.Tensor, torch.Tensor, int]:
+    """:func:`residual_quantiles` within each cell of ``X``: Mondrian
+    conformal half-widths, so the band follows ``X`` and the coverage
+    guarantee holds per cell.
+
+    ``cells`` is a :class:`models.conformal.Cells` (up to 16 equal cells of
+    ``[lo, hi)``; ``X`` outside clamps to an edge cell).  Returns
+    ``(halfwidths, m, n_nan)``: ``halfwidths`` fp32 ``[cells, Q]`` on the
+    inputs' device, ``m`` int64 ``[cells]`` (host) the non-NaN residuals of
+    each cell, ``n_nan`` the rows left out for a NaN residual or a NaN
+    ``X``.  Cell c's level L is its k-th smallest residual, ``k = ceil((m_c
+    + 1) * L)``, +inf when ``k > m_c``.  On the GPU every cell and level is
+    resolved by the same four streaming passes
+    (``ops/hip/resid_select_binned.h``) with one host read at the end; with
+    a ``process_group`` the pass histograms are all-reduced.
+    """
+    levels = check_levels(levels)
+    cp = _cell_params(cells)
+    if X.device.type == "cuda":
+        return _binned_select(X.contiguous().float(),
+                              labels.contiguous().float(),
+                              scores.contiguous().float(), levels, cp,
+                              process_group)
+    return _binned_select_cpu(reference.cells_of_cpu(X, *cp),
+                              reference.abs_residuals_cpu(labels, scores),
+                              levels, cp[0], process_group)
+
+
+def linear_split_binned_residual_quantiles(
+    X: torch.Tensor,
+    y: torch.Tensor,
+    ab,
+    levels,
+    cells,
+    test_frac: float = 0.2,
+    seed: int = 42,
+    process_group=None,
+) -> tuple[torch.Tensor, torch.Tensor, int]:
+    """:func:`binned_residual_quantiles` of the linear model ``ab =
+    [intercept, coef]`` over the TEST rows of ``random_split(X, y,
+    test_frac, seed)``, without materialising split or predictions (8
+    B/row: ``X`` is both the feature and the cell variable)."""
+    levels = check_levels(levels)
+    cp = _cell_params(cells)
+    if X.device.type == "cuda":
+        if not torch.is_tensor(ab):
+            ab = torch.tensor([float(ab[0]), float(ab[1])])
+        return _binned_select(
+            X.contiguous().float(), y.contiguous().float(), None, levels, cp,
+            process_group, ab=ab.to(X.device, torch.float32).contiguous(),
+            test_frac=test_frac, seed=seed)
+    _, _, X_te, y_te = reference.random_split_cpu(X, y, test_frac, seed)
+    yhat = reference.linear_score_cpu(X_te, float(ab[0]), float(ab[1]))
+    return _binned_select_cpu(reference.cells_of_cpu(X_te, *cp),
+                              reference.abs_residuals_cpu(y_te, yhat),
+                              levels, cp[0], process_group)
+
+
+def binned_interval_coverage(
+    X: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, halfwidths,
+    cells
+) -> torch.Tensor:
+    """How many rows lie inside the x-dependent band: int64 ``[cells, 1 +
+    4]`` on the inputs' device, per cell the rows with a non-NaN residual,
+    then per level those with ``|label - score| <= halfwidths[cell][q]`` —
+    one fused 12 B/row pass.  ``halfwidths`` is ``[cells, Q]``, Q <= 4;
+    missing levels are padded with -1 and count nothing.  Rows with a NaN
+    ``X`` belong to no cell."""
+    cp = _cell_params(cells)
+    h = torch.as_tensor(halfwidths, dtype=torch.float32).reshape(cp[0], -1)
+    if h.shape[1] > MAX_CONFORMAL_LEVELS:
+        raise ValueError("binned_interval_coverage: at most "
+                         f"{MAX_CONFORMAL_LEVELS} half-widths per cell")
+    pad = h.new_full((cp[0], MAX_CONFORMAL_LEVELS - h.shape[1]), -1.0)
+    h = torch.cat([h, pad], dim=1).contiguous()
+    if X.device.type == "cuda":
+        core = _core(X.device)
+        return core.binned_interval_coverage(
+            X.contiguous().float(), scores.contiguous().float(),
+            labels.contiguous().float(), h.to(X.device), *cp)
+    return reference.binned_interval_coverage_cpu(X, scores, labels, h, *cp)
 
 
 # --------------------------------------------------------------------------

@@ -45,6 +45,22 @@ at::Tensor resid_select_pass_hip(const at::Tensor& a, const at::Tensor& b,
                                  double test_frac, int64_t seed);
 at::Tensor resid_select_pick_hip(const at::Tensor& hist, at::Tensor state,
                                  int64_t pass, at::ArrayRef<double> levels);
+// resid_select_binned.hip
+at::Tensor resid_select_binned_pass_hip(
+    const at::Tensor& x, const at::Tensor& a,
+    const c10::optional<at::Tensor>& b, const at::Tensor& state, int64_t pass,
+    int64_t nq, int64_t cells, double lo, double scale,
+    const c10::optional<at::Tensor>& ab, double test_frac, int64_t seed);
+at::Tensor resid_select_binned_pick_hip(const at::Tensor& hist,
+                                        at::Tensor state, int64_t pass,
+                                        at::ArrayRef<double> levels,
+                                        int64_t cells);
+at::Tensor binned_interval_coverage_hip(const at::Tensor& x,
+                                        const at::Tensor& s,
+                                        const at::Tensor& l,
+                                        const at::Tensor& halfwidths,
+                                        int64_t cells, double lo,
+                                        double scale);
 // mlp_small.hip
 std::tuple<at::Tensor, at::Tensor> expand1d_bf16_hip(
     const at::Tensor& x, const at::Tensor& w,
@@ -140,6 +156,13 @@ TORCH_LIBRARY(bodywork_hip, m) {
         "int nq, Tensor? ab, float test_frac, int seed) -> Tensor");
   m.def("resid_select_pick(Tensor hist, Tensor(a!) state, int pass_index, "
         "float[] levels) -> Tensor");
+  m.def("resid_select_binned_pass(Tensor x, Tensor a, Tensor? b, Tensor state, "
+        "int pass_index, int nq, int cells, float lo, float scale, "
+        "Tensor? ab, float test_frac, int seed) -> Tensor");
+  m.def("resid_select_binned_pick(Tensor hist, Tensor(a!) state, "
+        "int pass_index, float[] levels, int cells) -> Tensor");
+  m.def("binned_interval_coverage(Tensor x, Tensor s, Tensor l, "
+        "Tensor halfwidths, int cells, float lo, float scale) -> Tensor");
   m.def("expand1d_bf16(Tensor x, Tensor w, Tensor? b, bool relu, "
         "Tensor? mask, bool emit_mask, Tensor? n_dev) -> (Tensor, Tensor)");
   m.def("rowdot_bf16(Tensor h, Tensor w, Tensor bias) -> Tensor");
@@ -197,6 +220,9 @@ TORCH_LIBRARY_IMPL(bodywork_hip, CUDA, m) {
   m.impl("interval_coverage", interval_coverage_hip);
   m.impl("resid_select_pass", resid_select_pass_hip);
   m.impl("resid_select_pick", resid_select_pick_hip);
+  m.impl("resid_select_binned_pass", resid_select_binned_pass_hip);
+  m.impl("resid_select_binned_pick", resid_select_binned_pick_hip);
+  m.impl("binned_interval_coverage", binned_interval_coverage_hip);
   m.impl("expand1d_bf16", expand1d_bf16_hip);
   m.impl("rowdot_bf16", rowdot_bf16_hip);
   m.impl("coldot_bf16", coldot_bf16_hip);

@@ -320,6 +320,63 @@ def interval_coverage_cpu(scores, labels, halfwidths) -> torch.Tensor:
     return torch.tensor([float(r.size), *counts], dtype=torch.float64)
 
 
+def cells_of_cpu(x, n: int, lo, scale) -> np.ndarray:
+    """The cell rule of ``ops/hip/resid_select_binned.h`` in numpy float32,
+    one rounded operation per step: ``t = (x - lo) * scale``; cell -1 (none)
+    if ``t`` is NaN, else 0 if ``t < 0``, else ``n - 1`` if ``t >= n``, else
+    ``trunc(t)``.  int64, one per element of ``x``."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = (_f32(x) - np.float32(lo)) * np.float32(scale)
+        under = t < np.float32(0)
+        over = t >= np.float32(n)
+        nan = np.isnan(t)
+    cell = np.full(t.shape, -1, dtype=np.int64)
+    inside = ~(under | over | nan)
+    cell[inside] = t[inside].astype(np.int64)  # truncation
+    cell[under] = 0
+    cell[over] = n - 1
+    return cell
+
+
+def binned_select_residuals_cpu(cell: np.ndarray, r: np.ndarray, levels,
+                                n: int):
+    """``(halfwidths fp32 [n, Q], m int64 [n], n_nan)``:
+    :func:`select_residuals_cpu` of the rows of each cell; a row without a
+    cell is left out and counted with the NaN residuals."""
+    hw = torch.empty((n, len(levels)), dtype=torch.float32)
+    m = torch.zeros(n, dtype=torch.int64)
+    n_nan = int(np.count_nonzero(cell < 0))
+    for c in range(n):
+        hw[c], m[c], nan_c = select_residuals_cpu(r[cell == c], levels)
+        n_nan += nan_c
+    return hw, m, n_nan
+
+
+def binned_residual_quantiles_cpu(x, labels, scores, levels, n, lo, scale):
+    """Oracle of ``ops/hip/resid_select_binned.hip`` and the CPU path of
+    :func:`ops.binned_residual_quantiles`."""
+    return binned_select_residuals_cpu(
+        cells_of_cpu(x, n, lo, scale), abs_residuals_cpu(labels, scores),
+        levels, n)
+
+
+def binned_interval_coverage_cpu(x, scores, labels, halfwidths, n, lo,
+                                 scale) -> torch.Tensor:
+    """int64 ``[n, 5]``: per cell the rows with a non-NaN residual, then per
+    level the rows with ``|label - score| <= halfwidths[cell, q]`` — the
+    oracle of ``binned_coverage_kernel``.  ``halfwidths`` is ``[n, 4]``."""
+    cell = cells_of_cpu(x, n, lo, scale)
+    r = abs_residuals_cpu(labels, scores)
+    h = _f32(halfwidths).reshape(n, 4)
+    out = np.zeros((n, 5), dtype=np.int64)
+    for c in range(n):
+        rc = r[cell == c]
+        rc = rc[~np.isnan(rc)]
+        out[c] = [rc.size, *(np.count_nonzero(rc <= h[c, q])
+                             for q in range(4))]
+    return torch.from_numpy(out)
+
+
 # --------------------------------------------------------------------------
 # GEMM oracle
 # --------------------------------------------------------------------------

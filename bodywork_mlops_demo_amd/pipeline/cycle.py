@@ -305,6 +305,7 @@ def run_cycle(
     capture: dict | None = None,
     drift_monitor=None,
     conformal_levels=None,
+    conformal_bins=None,
 ) -> dict:
     """Run one full cycle; returns per-phase timings + metrics.
 
@@ -337,7 +338,9 @@ def run_cycle(
     gains ``conformal``, the :class:`models.conformal.Calibration`) and
     stage 4 checks their coverage on day t+1 (``pi<pct>_*`` in ``online``
     and the test-metrics CSV).  A ``skip_train`` cycle checks the deployed
-    model's calibration.
+    model's calibration.  ``conformal_bins`` goes to stage 1 with them: the
+    calibration is then binned over X and stage 4 checks the x-dependent
+    band, overall and per cell.
     """
     device = state.device
     dev_cuda = device.startswith("cuda")
@@ -398,6 +401,7 @@ def run_cycle(
         return_model=True,
         model_cache=scorer_cache,
         conformal_levels=conformal_levels,
+        conformal_bins=conformal_bins,
     )
     finish = dict(capture=capture, drift_monitor=drift_monitor,
                   conformal=None, process_group=process_group)

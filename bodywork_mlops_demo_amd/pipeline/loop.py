@@ -43,6 +43,7 @@ def run_loop(
     ks_alpha: float = 1e-3,
     ks_threshold: float | None = None,
     conformal_levels=None,
+    conformal_bins=None,
 ) -> list[dict]:
     """Run ``days`` cycles.
 
@@ -120,6 +121,7 @@ def run_loop(
             scorer_cache=scorer_cache, skip_train=skip,
             drift_monitor=monitor,
             conformal_levels=conformal_levels,
+            conformal_bins=conformal_bins,
         )
         results.append(r)
         if retrain_policy == "ks":
@@ -207,7 +209,12 @@ def main(argv=None) -> None:
                    help="calibrate prediction intervals at these confidence "
                         "levels at every training and check their coverage "
                         "every day, e.g. 0.9,0.95 (at most 4)")
+    p.add_argument("--conformal-bins", default=None, type=int, metavar="N",
+                   help="with --conformal: calibrate within each of N "
+                        "(1..16) equal cells of X, for an x-dependent band")
     args = p.parse_args(argv)
+    if args.conformal_bins is not None and not args.conformal:
+        p.error("--conformal-bins needs --conformal")
     # env flags so the models built inside the cycle opt in
     args.model, env = resolve_model(args.model)
     if env:
@@ -222,6 +229,7 @@ def main(argv=None) -> None:
         drift_threshold=args.drift_threshold,
         drift_monitor=args.drift_monitor, ks_alpha=args.ks_alpha,
         ks_threshold=args.ks_threshold, conformal_levels=args.conformal,
+        conformal_bins=args.conformal_bins,
     )
     if args.json_out:
         with open(args.json_out, "w") as f:

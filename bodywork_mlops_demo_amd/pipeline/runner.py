@@ -480,12 +480,20 @@ def main(argv=None) -> None:
                         "0.9,0.95: the train stage calibrates them and the "
                         "load-test stage checks their coverage (handed to "
                         "the stages as BODYWORK_AMD_CONFORMAL)")
+    p.add_argument("--conformal-bins", default=None, type=int, metavar="N",
+                   help="with --conformal: the train stage calibrates within "
+                        "each of N (1..16) equal cells of X (handed to it as "
+                        "BODYWORK_AMD_CONFORMAL_BINS)")
     args = p.parse_args(argv)
+    if args.conformal_bins is not None and not args.conformal:
+        p.error("--conformal-bins needs --conformal")
     if args.conformal:
         from bodywork_mlops_demo_amd.stages.train import parse_levels
 
         parse_levels(args.conformal)  # fail here, not in a stage
         os.environ["BODYWORK_AMD_CONFORMAL"] = args.conformal
+    if args.conformal_bins is not None:
+        os.environ["BODYWORK_AMD_CONFORMAL_BINS"] = str(args.conformal_bins)
     runner = PipelineRunner(args.config, store_uri=args.store,
                             secrets_file=args.secrets,
                             isolate_envs=args.isolate_envs)

@@ -21,7 +21,11 @@ Extensions beyond the reference (batched GPU serving):
   ``X-Interval-Halfwidths`` headers (the band is constant, the client
   forms the intervals); ``/reload/v1`` and ``/healthz`` report the levels
   as ``interval_levels``.  Requests without ``confidence`` to an
-  uncalibrated model get exactly the responses described above.
+  uncalibrated model get exactly the responses described above.  With a
+  BINNED calibration the JSON endpoints take each row's half-width from
+  the cell of its ``X`` (``Calibration.halfwidth_at``), and the binary
+  endpoint adds ``X-Interval-Cells: n,lo,hi`` and
+  ``X-Interval-Cell-Halfwidths`` (row-major ``[cells][levels]``).
 
 Served by uvicorn (ASGI) instead of the reference's Flask dev server —
 one replica process per GPU, model resident in HBM, hipGraph-captured
@@ -72,8 +76,9 @@ def create_app(store: ArtefactStore, device: str = "cpu",
         state["model_date"] = str(model_date)
         state["calibration"] = getattr(model, "conformal_", None)
 
-    def halfwidth(payload) -> tuple[float, float] | None:
-        """(level, half-width) for a request that carries ``confidence``."""
+    def halfwidth(payload):
+        """(level, half-width of each row) for a request that carries
+        ``confidence``."""
         if "confidence" not in payload:
             return None
         cal = state.get("calibration")
@@ -84,13 +89,15 @@ def create_app(store: ArtefactStore, device: str = "cpu",
                     f"no interval calibrated for confidence {level:g}; "
                     "available levels: none (the model was trained without "
                     "conformal calibration)")
-            return level, cal.halfwidth(level)
+            x = np.atleast_1d(np.asarray(payload["X"], dtype=np.float32))
+            return level, cal.halfwidth_at(level, x.reshape(-1))
         except (TypeError, ValueError) as e:
             raise _NoInterval(str(e)) from e
 
     def interval_fields(preds, hw, scalar: bool) -> dict:
-        level, h = hw
-        pairs = [[_bound(float(p) - h), _bound(float(p) + h)] for p in preds]
+        level, hs = hw
+        pairs = [[_bound(float(p) - float(h)), _bound(float(p) + float(h))]
+                 for p, h in zip(preds, hs)]
         return {"interval": pairs[0] if scalar else pairs,
                 "confidence": level}
 
@@ -161,6 +168,11 @@ def create_app(store: ArtefactStore, device: str = "cpu",
                 repr(v) for v in cal.levels)
             headers["X-Interval-Halfwidths"] = ",".join(
                 repr(v) for v in cal.halfwidths)
+            if cal.cells is not None:
+                g = cal.cells
+                headers["X-Interval-Cells"] = f"{g.n},{g.lo!r},{g.hi!r}"
+                headers["X-Interval-Cell-Halfwidths"] = ",".join(
+                    repr(v) for row in cal.cell_halfwidths for v in row)
         return Response(content=preds.astype(np.float32).tobytes(),
                         media_type="application/octet-stream",
                         headers=headers)

@@ -161,26 +161,52 @@ def _calibration(conformal, store):
     return cal
 
 
+def _covered(count: float, n: float, level: float) -> tuple[float, int]:
+    """(coverage, ok): ok is 0 when the coverage of ``n`` rows falls below
+    the one-sided binomial floor of ``level``."""
+    if n <= 0:
+        return float("nan"), 1
+    coverage = count / n
+    floor = level - COVERAGE_Z * (level * (1.0 - level) / n) ** 0.5
+    return coverage, 0 if coverage < floor else 1
+
+
 def coverage_metrics(cal, scores: torch.Tensor, labels: torch.Tensor,
-                     process_group=None) -> dict:
+                     process_group=None, X: torch.Tensor | None = None) -> dict:
     """``pi<pct>_coverage`` / ``_halfwidth`` / ``_ok`` per level of ``cal``,
-    in that order level by level, from one coverage pass."""
+    in that order level by level, from one coverage pass.  A binned
+    calibration is checked as served, through the x-dependent band of
+    ``X``: the coverage is the overall one, and per level
+    ``pi<pct>_cell_coverage`` (a list), ``pi<pct>_worst_cell_coverage`` and
+    ``pi<pct>_cells_ok`` (the same bound with each cell's own row count)
+    follow ``_ok``."""
     from bodywork_mlops_demo_amd.models.conformal import level_name
 
-    counts = ops.interval_coverage(scores, labels, cal.halfwidths)
+    binned = cal.cells is not None
+    if binned:
+        counts = ops.binned_interval_coverage(
+            X.to(scores.device), scores, labels, cal.cell_halfwidths,
+            cal.cells)
+    else:
+        counts = ops.interval_coverage(scores, labels, cal.halfwidths)
     if process_group is not None:
         counts = ops.allreduce_counts(counts, process_group)
-    counts = counts.tolist()
-    n = counts[0]
+    per_cell = counts.tolist() if binned else []
+    counts = counts.sum(dim=0).tolist() if binned else counts.tolist()
     out = {}
     for q, (level, h) in enumerate(zip(cal.levels, cal.halfwidths)):
         pct = level_name(level)
-        coverage = counts[1 + q] / n if n > 0 else float("nan")
-        floor = level - COVERAGE_Z * (level * (1.0 - level) / n) ** 0.5 \
-            if n > 0 else 0.0
+        coverage, ok = _covered(counts[1 + q], counts[0], level)
         out[f"pi{pct}_coverage"] = coverage
         out[f"pi{pct}_halfwidth"] = h
-        out[f"pi{pct}_ok"] = 0 if coverage < floor else 1
+        out[f"pi{pct}_ok"] = ok
+        if binned:
+            cells = [_covered(row[1 + q], row[0], level) for row in per_cell]
+            seen = [c for c, _ in cells if c == c]
+            out[f"pi{pct}_cell_coverage"] = [c for c, _ in cells]
+            out[f"pi{pct}_worst_cell_coverage"] = (min(seen) if seen
+                                                   else float("nan"))
+            out[f"pi{pct}_cells_ok"] = min(ok_c for _, ok_c in cells)
     return out
 
 
@@ -211,7 +237,10 @@ def run(
     ``pi<pct>_coverage``, ``pi<pct>_halfwidth`` and ``pi<pct>_ok`` — 1
     unless the coverage falls below ``level - z * sqrt(level * (1 - level)
     / n)`` with z = 3.09, a one-sided 1e-3 binomial test.  These columns
-    come last.  With a ``process_group`` the counts are all-reduced.
+    come last.  With a ``process_group`` the counts are all-reduced.  A
+    binned calibration is checked through its x-dependent band
+    (``ops.binned_interval_coverage``) and adds the per-cell figures
+    described at :func:`coverage_metrics`.
 
     ``scorer`` bypasses HTTP entirely (in-process serving replica) for the
     hermetic pipeline/bench path; ``data`` skips the store read when the
@@ -273,9 +302,10 @@ def run(
     pi_keys: tuple = ()
     if conformal:
         cal = _calibration(conformal, store)
-        cov = coverage_metrics(cal, scores, labels, process_group)
+        cov = coverage_metrics(cal, scores, labels, process_group, X=X)
         metrics.update(cov)
-        pi_keys = tuple(cov)
+        # the per-cell list stays in the returned metrics, out of the CSV
+        pi_keys = tuple(k for k, v in cov.items() if not isinstance(v, list))
     log.info(f"live-service metrics on {n} rows: {metrics}")
 
     if persist:

@@ -25,7 +25,11 @@ from bodywork_mlops_demo_amd.models import (
     GPUPolyRegressor,
     GPUPolyRegressorCV,
 )
-from bodywork_mlops_demo_amd.models.conformal import Calibration, level_name
+from bodywork_mlops_demo_amd.models.conformal import (
+    Calibration,
+    Cells,
+    level_name,
+)
 from bodywork_mlops_demo_amd.monitoring import stage_guard
 from bodywork_mlops_demo_amd.store import ArtefactStore, contract, open_store
 from bodywork_mlops_demo_amd.utils.logging import configure_logger
@@ -52,6 +56,7 @@ def run(
     return_model: bool = False,
     model_cache: dict | None = None,
     conformal_levels=None,
+    conformal_bins=None,
 ):
     """Train and persist; returns the offline metrics record
     (or ``(metrics, model)`` when ``return_model``).
@@ -65,10 +70,18 @@ def run(
     half-widths go onto the model (``conformal_``, and into its artefact)
     and are appended to the model-metrics CSV as ``pi_cal_n`` and one
     ``pi<pct>_halfwidth`` per level.  Without levels neither changes.
+
+    ``conformal_bins`` (1..16, needs ``conformal_levels``) also calibrates
+    the levels within each of that many equal cells of X over [0, 100)
+    (``ops.binned_residual_quantiles``), so the served band follows X; the
+    marginal half-widths above and the metrics CSV stay as they are.
     """
     device = device or default_device()
     levels = (ops.check_levels(conformal_levels)
               if conformal_levels is not None else None)
+    if conformal_bins is not None and levels is None:
+        raise ValueError("conformal_bins needs conformal_levels")
+    cells = Cells(conformal_bins) if conformal_bins is not None else None
     if data is None:
         y_np, X_np, data_date = store.get_all_datasets()
         X = torch.from_numpy(X_np).to(device)
@@ -155,6 +168,16 @@ def run(
                 y_test, yhat, levels, process_group=process_group)
         model.conformal_ = Calibration.from_select(levels, selected,
                                                    date=data_date)
+        if cells is not None:
+            if model_type == "linear":
+                binned = ops.linear_split_binned_residual_quantiles(
+                    X, y, ab, levels, cells, 0.2, seed=42,
+                    process_group=process_group)
+            else:
+                binned = ops.binned_residual_quantiles(
+                    X_test, y_test, yhat, levels, cells,
+                    process_group=process_group)
+            model.conformal_ = model.conformal_.with_cells(cells, binned)
         log.info(f"conformal calibration: {model.conformal_}")
 
     if rank == 0:
@@ -201,10 +224,20 @@ def main(argv=None) -> None:
                    help="calibrate prediction intervals at these confidence "
                         "levels, e.g. 0.9,0.95 (at most 4, each in (0, 1)); "
                         "default: $BODYWORK_AMD_CONFORMAL")
+    p.add_argument("--conformal-bins", type=int, metavar="N",
+                   default=(int(os.environ["BODYWORK_AMD_CONFORMAL_BINS"])
+                            if os.environ.get("BODYWORK_AMD_CONFORMAL_BINS")
+                            else None),
+                   help="also calibrate the levels within each of N (1..16) "
+                        "equal cells of X, for an x-dependent band; needs "
+                        "--conformal; default: $BODYWORK_AMD_CONFORMAL_BINS")
     args = p.parse_args(argv)
+    if args.conformal_bins is not None and not args.conformal:
+        p.error("--conformal-bins needs --conformal")
     with stage_guard(STAGE_NAME, exit_on_error=True):
         run(open_store(args.store), model_type=args.model, device=args.device,
-            mlp_steps=args.mlp_steps, conformal_levels=args.conformal)
+            mlp_steps=args.mlp_steps, conformal_levels=args.conformal,
+            conformal_bins=args.conformal_bins)
 
 
 if __name__ == "__main__":
