@@ -24,6 +24,9 @@ stays valid), dgrad multiplies it with an e4m3 shadow of ``W2`` and
 applies the 1-bit ReLU mask in the epilogue, wgrad multiplies the
 byte-transposed e4m3 ``h1`` of the forward with the byte-transposed
 ``dz2``.  Everything else in the backward stays bf16/fp32.
+Opt-in scoring (``fp4_scoring=True`` / ``BODYWORK_MLP_FP4=1``): layer 1
+and the h2 GEMM + head run on MXFP4 operands (e2m1 codes, per-32-element
+block scales held in device tensors).
 
 Artefact: a *real sklearn ``MLPRegressor``* with ``coefs_``/``intercepts_``
 injected, so ``joblib.load`` + ``predict`` work with stock sklearn
@@ -42,6 +45,12 @@ from bodywork_mlops_demo_amd.models import conformal
 from bodywork_mlops_demo_amd.utils.logging import configure_logger
 
 log = configure_logger(__name__)
+
+
+def _os_environ_flag(name: str) -> bool:
+    import os
+
+    return os.environ.get(name, "0") == "1"
 
 
 class GPUMLPRegressor:
@@ -63,7 +72,8 @@ class GPUMLPRegressor:
     def __init__(self, hidden: int = 4096, device="cpu", seed: int = 7,
                  fp8_scoring: bool | None = None,
                  fp8_training: bool | None = None,
-                 fp8_backward: bool | None = None):
+                 fp8_backward: bool | None = None,
+                 fp4_scoring: bool | None = None):
         self.hidden = hidden
         self.device = canonical_device(device)
         # opt-in MX-fp8 scoring forward (2x-rate K=128 scaled MFMA for the
@@ -77,6 +87,13 @@ class GPUMLPRegressor:
         self._w2_q8: torch.Tensor | None = None
         self._e_w2: int | None = None
         self._e_h1: int | None = None
+        # opt-in MXFP4 scoring forward (fp4 form of the same MFMA, true
+        # per-32-element block scales held in device tensors: nothing is
+        # frozen at calibration).  Wins over fp8_scoring when both are set.
+        if fp4_scoring is None:
+            fp4_scoring = _os_environ_flag("BODYWORK_MLP_FP4")
+        self.fp4_scoring = fp4_scoring
+        self._w2_q4: tuple[torch.Tensor, torch.Tensor] | None = None
         # opt-in MX-fp8 TRAINING forward: the h2 = relu(h1 @ W2 + b2) GEMM
         # runs on e4m3 operands (with this flag alone the two backward
         # GEMMs stay bf16 and the gradients pass straight through the
@@ -122,6 +139,7 @@ class GPUMLPRegressor:
         for name in ("w1", "b1", "W2", "b2", "w3", "b3"):
             setattr(self, name, getattr(self, name).to(d))
         self._w2_q8 = None  # fp8 shadow re-created lazily on new device
+        self._w2_q4 = None
         self._w2_q8_tr = None
         self._w2t_q8_tr = None
         self._refresh_bf16()
@@ -154,6 +172,7 @@ class GPUMLPRegressor:
             getattr(self, name).copy_(getattr(other, name).to(self.device))
         self.conformal_ = other.conformal_
         self._refresh_fp8()
+        self._refresh_fp4()
         self._refresh_fp8_train()
         return True
 
@@ -182,6 +201,19 @@ class GPUMLPRegressor:
             bound = 1.8 * self.w1.abs().max().item() \
                 + self.b1.abs().max().item()
             self._e_h1 = ops.e4m3_exponent(bound)
+
+    # -- MXFP4 scoring shadow ---------------------------------------------
+    def _ensure_fp4_weights(self) -> None:
+        """Quantise ``W2w_bf`` to (codes, block scales) once; tensor in,
+        tensors out, no host sync."""
+        if self._w2_q4 is None:
+            self._w2_q4 = ops.quantize_mxfp4(self.W2w_bf)
+
+    def _refresh_fp4(self) -> None:
+        """Requantise codes AND scales IN PLACE after a weight change, so a
+        captured serving graph follows a redeploy with fresh block scales."""
+        if self._w2_q4 is not None:
+            ops.quantize_mxfp4(self.W2w_bf, out=self._w2_q4)
 
     # -- MX-fp8 training shadow ------------------------------------------
     def _init_fp8_train_state(self) -> None:
@@ -308,6 +340,17 @@ class GPUMLPRegressor:
             h1, m1 = ops.expand1d_bf16(xn, self.w1_bf, self.b1_bf, relu=True,
                                        emit_mask=True)
             h2, m2 = ops.linear_relu_mask_bf16(h1, self.W2w_bf, self.b2_bf)
+        elif self._use_fp4(xn.shape[0]):
+            # fp4 scoring forward, two kernels: the fused layer-1 expand
+            # emitting MXFP4 codes + block scales, then the fp4 scaled-MFMA
+            # h2 GEMM with the relu+rowdot head in its epilogue
+            self._ensure_fp4_weights()
+            h1q, h1s = ops.expand1d_mxfp4(xn, self.w1_bf, self.b1_bf,
+                                          n_dev=n_dev)
+            yhat = ops.gemm_mxfp4_relu_dot(h1q, h1s, *self._w2_q4, self.b2,
+                                           self.w3, n_dev=n_dev)
+            yhat = yhat + self.b3
+            return yhat, (h1q, h1s), None, xn, None, None
         elif self._use_fp8(xn.shape[0]):
             # fp8 scoring forward in TWO kernels total: (1) fused layer-1
             # expand emitting e4m3 directly (1 HBM byte/element), (2) the
@@ -344,6 +387,11 @@ class GPUMLPRegressor:
         (the K=128 scaled-MFMA kernel serves M%256==0; other batch sizes
         take the bf16 kernel)."""
         return (self.fp8_scoring and self.device.type == "cuda"
+                and m % 256 == 0 and self.hidden % 256 == 0)
+
+    def _use_fp4(self, m: int) -> bool:
+        """MXFP4 scoring: opt-in, GPU-only, gated like :meth:`_use_fp8`."""
+        return (self.fp4_scoring and self.device.type == "cuda"
                 and m % 256 == 0 and self.hidden % 256 == 0)
 
     def _use_fused_head(self, m: int) -> bool:
@@ -505,6 +553,7 @@ class GPUMLPRegressor:
         self.b2_bf.copy_(self.b2.bfloat16())
         self.w3_bf.copy_(self.w3.bfloat16())
         self._refresh_fp8()
+        self._refresh_fp4()
         self._refresh_fp8_train()
         return self
 
@@ -714,6 +763,8 @@ class GPUMLPRegressor:
         self._w2_q8 = None
         self._e_w2 = None
         self._e_h1 = None
+        self.fp4_scoring = _os_environ_flag("BODYWORK_MLP_FP4")
+        self._w2_q4 = None
         self.fp8_backward = _os.environ.get("BODYWORK_MLP_FP8_BWD",
                                             "0") == "1"
         self.fp8_training = self.fp8_backward or _os.environ.get(

@@ -33,6 +33,11 @@ here every computational primitive is a first-class gfx950 kernel
                        such a band
 - ``gemm_bf16``      — MFMA (v_mfma_f32_16x16x32_bf16) LDS-tiled dense
                        GEMM with fused bias+ReLU epilogue for the MLP path
+- ``gemm_mxfp4_nt``  — MXFP4 (e2m1 codes, per-32-element E8M0 block scales)
+                       GEMM on the fp4 form of the scaled K=128 MFMA, with
+                       ``quantize_mxfp4``, the fused layer 1
+                       ``expand1d_mxfp4`` and the fused scoring head
+                       ``gemm_mxfp4_relu_dot`` (opt-in 4-bit MLP scoring)
 
 Dispatch policy: on a CUDA/HIP device the in-tree ``_hipcore`` extension
 is REQUIRED — if it is missing the ops raise instead of silently falling
@@ -1225,6 +1230,115 @@ def gemm_mx8_nt_fmt(
             mask.contiguous() if mask is not None else None, out_fp32)
     return reference.gemm_mx8_nt_fmt_cpu(a8, ea, b8, eb, a_fmt, b_fmt, mask,
                                          out_fp32)
+
+
+# --------------------------------------------------------------------------
+# MXFP4 scoring: e2m1 codes with per-32-element E8M0 block scales
+# --------------------------------------------------------------------------
+
+def quantize_mxfp4(
+    x: torch.Tensor,
+    out: tuple[torch.Tensor, torch.Tensor] | None = None,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """x ``[R, K]`` (fp32 or bf16) -> ``(q, s)``: OCP e2m1 codes, uint8 ``[R,
+    K/2]`` with element 2i in the low nibble of byte i, and one E8M0 byte
+    per 32 consecutive K elements of a row, uint8 ``[R*K/32]``.
+
+    Per block the exponent is the smallest ``e`` with ``amax / 2^e <= 6``
+    (from the float fields; 0 for a zero or non-finite block), the elements
+    are ``x / 2^e`` rounded to the nearest of 0, 0.5, 1, 1.5, 2, 3, 4, 6,
+    ties to the even code, saturating.  The ORDER of ``s`` is private to
+    these ops (the GEMM's K-loop order); ``reference.mxfp4_decode_cpu`` is
+    the logical decode.  Requires R%64==0 and K%256==0.  ``out=(q, s)``
+    writes into existing tensors (a hot redeploy keeps its pointers).
+    CPU oracle: ``reference.quantize_mxfp4_cpu``."""
+    if x.device.type == "cuda":
+        core = _core(x.device)
+        R, K = x.shape
+        if out is None:
+            out = (torch.empty((R, K // 2), dtype=torch.uint8,
+                               device=x.device),
+                   torch.empty(R * K // 32, dtype=torch.uint8,
+                               device=x.device))
+        core.quantize_mxfp4(x.contiguous(), out[0], out[1])
+        return out
+    q, s = reference.quantize_mxfp4_cpu(x)
+    if out is not None:
+        out[0].copy_(q)
+        out[1].copy_(s)
+        return out
+    return q, s
+
+
+def expand1d_mxfp4(
+    x: torch.Tensor,
+    w: torch.Tensor,
+    b: torch.Tensor | None,
+    n_dev: torch.Tensor | None = None,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """h = relu(x*w + b) emitted DIRECTLY as MXFP4 ``(q, s)`` — the fp4
+    scoring forward's fused layer 1 (0.53 HBM bytes per element).  Equals
+    ``quantize_mxfp4`` of the fp32 activation.  ``n_dev``: live row count as
+    in :func:`expand1d_e4m3` (rows past it are left unwritten; the CPU
+    oracle computes every row).  Requires n%64==0 and H%256==0."""
+    if x.device.type == "cuda":
+        core = _core(x.device)
+        return core.expand1d_mxfp4(
+            x.contiguous().float(), w.contiguous(),
+            b.contiguous() if b is not None else None, n_dev)
+    h = x.float()[:, None] * w.float()[None, :]
+    if b is not None:
+        h = h + b.float()[None, :]
+    return reference.quantize_mxfp4_cpu(torch.relu(h))
+
+
+def gemm_mxfp4_nt(
+    aq: torch.Tensor,
+    sa: torch.Tensor,
+    bq: torch.Tensor,
+    sb: torch.Tensor,
+    bias: torch.Tensor | None = None,
+    relu: bool = False,
+    out_fp32: bool = False,
+) -> torch.Tensor:
+    """C[M,N] = A[M,K] . B[N,K]^T over MXFP4 operands (``quantize_mxfp4``
+    output), fp32 accumulation, optional fused bias+relu epilogue.
+
+    Runs the fp4 form of the gfx950 scaled MFMA
+    (v_mfma_scale_f32_16x16x128_f8f6f4, cbsz = blgp = 4) with true per-block
+    scales fetched in the K-loop (ops/hip/gemm_mx4.hip).  Requires
+    M%256==0, N%256==0, K%256==0.  CPU oracle: decode + fp32 matmul."""
+    if aq.device.type == "cuda":
+        core = _core(aq.device)
+        return core.gemm_mxfp4_nt(
+            aq.contiguous(), sa.contiguous(), bq.contiguous(),
+            sb.contiguous(),
+            bias.contiguous() if bias is not None else None, relu, out_fp32)
+    return reference.gemm_mxfp4_nt_cpu(aq, sa, bq, sb, bias, relu, out_fp32)
+
+
+def gemm_mxfp4_relu_dot(
+    aq: torch.Tensor,
+    sa: torch.Tensor,
+    bq: torch.Tensor,
+    sb: torch.Tensor,
+    b2: torch.Tensor,
+    w3: torch.Tensor,
+    n_dev: torch.Tensor | None = None,
+) -> torch.Tensor:
+    """y[M] = Σ_col relu(A·Bᵀ + b2) * w3 over MXFP4 operands — the fp4
+    scoring forward's h2 GEMM and rowdot head in ONE kernel (the twin of
+    :func:`gemm_mx8_relu_dot`, same ``n_dev`` contract: row tiles past the
+    live count return at once, rows ``>= n_dev`` of y are exactly 0 and
+    whatever their codes and scales hold reaches no live row)."""
+    if aq.device.type == "cuda":
+        core = _core(aq.device)
+        return core.gemm_mxfp4_relu_dot(
+            aq.contiguous(), sa.contiguous(), bq.contiguous(),
+            sb.contiguous(), b2.contiguous(), w3.contiguous(), n_dev)
+    h2 = reference.gemm_mxfp4_nt_cpu(aq, sa, bq, sb, bias=b2, relu=True,
+                                     out_fp32=True)
+    return _zero_dead_rows(h2 @ w3.detach().cpu().float(), n_dev)
 
 
 def linear_relu_dot_bf16(

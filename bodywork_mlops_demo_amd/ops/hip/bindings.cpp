@@ -119,6 +119,20 @@ at::Tensor gemm_mx8_nt_fmt_hip(const at::Tensor& a8, int64_t ea,
                                int64_t a_fmt, int64_t b_fmt,
                                const c10::optional<at::Tensor>& mask,
                                bool out_fp32);
+// gemm_mx4.hip — MXFP4 (e2m1 codes, per-32 E8M0 block scales) scoring path
+void quantize_mxfp4_hip(const at::Tensor& x, at::Tensor q, at::Tensor s);
+std::tuple<at::Tensor, at::Tensor> expand1d_mxfp4_hip(
+    const at::Tensor& x, const at::Tensor& w,
+    const c10::optional<at::Tensor>& b,
+    const c10::optional<at::Tensor>& n_dev);
+at::Tensor gemm_mxfp4_nt_hip(const at::Tensor& aq, const at::Tensor& as,
+                             const at::Tensor& bq, const at::Tensor& bs,
+                             const c10::optional<at::Tensor>& bias, bool relu,
+                             bool out_fp32);
+at::Tensor gemm_mxfp4_relu_dot_hip(const at::Tensor& aq, const at::Tensor& as,
+                                   const at::Tensor& bq, const at::Tensor& bs,
+                                   const at::Tensor& b2, const at::Tensor& w3,
+                                   const c10::optional<at::Tensor>& n_dev);
 // optim.hip
 void adam_step_hip(at::Tensor p, const at::Tensor& g, at::Tensor m,
                    at::Tensor v, const c10::optional<at::Tensor>& p_bf16,
@@ -189,6 +203,13 @@ TORCH_LIBRARY(bodywork_hip, m) {
   m.def("expand1d_bf16_e5m2(Tensor x, Tensor w, Tensor mask, Tensor e_dev) "
         "-> (Tensor, Tensor)");
   m.def("transpose_u8(Tensor src) -> Tensor");
+  m.def("quantize_mxfp4(Tensor x, Tensor(a!) q, Tensor(b!) s) -> ()");
+  m.def("expand1d_mxfp4(Tensor x, Tensor w, Tensor? b, Tensor? n_dev) -> "
+        "(Tensor, Tensor)");
+  m.def("gemm_mxfp4_nt(Tensor aq, Tensor sa, Tensor bq, Tensor sb, "
+        "Tensor? bias, bool relu, bool out_fp32) -> Tensor");
+  m.def("gemm_mxfp4_relu_dot(Tensor aq, Tensor sa, Tensor bq, Tensor sb, "
+        "Tensor b2, Tensor w3, Tensor? n_dev) -> Tensor");
   m.def("gemm_mx8_nt_fmt(Tensor a8, int ea, Tensor? ea_dev, Tensor b8, "
         "int eb, Tensor? eb_dev, int a_fmt, int b_fmt, Tensor? mask, "
         "bool out_fp32) -> Tensor");
@@ -240,6 +261,10 @@ TORCH_LIBRARY_IMPL(bodywork_hip, CUDA, m) {
   m.impl("quantize_e5m2", quantize_e5m2_hip);
   m.impl("expand1d_bf16_e5m2", expand1d_bf16_e5m2_hip);
   m.impl("transpose_u8", transpose_u8_hip);
+  m.impl("quantize_mxfp4", quantize_mxfp4_hip);
+  m.impl("expand1d_mxfp4", expand1d_mxfp4_hip);
+  m.impl("gemm_mxfp4_nt", gemm_mxfp4_nt_hip);
+  m.impl("gemm_mxfp4_relu_dot", gemm_mxfp4_relu_dot_hip);
   m.impl("gemm_mx8_nt_fmt", gemm_mx8_nt_fmt_hip);
   m.impl("gemm8_relu_dot_bf16", gemm8_relu_dot_bf16_hip);
   m.impl("adam_step", adam_step_hip);

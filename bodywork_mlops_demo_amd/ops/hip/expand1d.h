@@ -114,6 +114,67 @@ __device__ __forceinline__ void e1d_store_e5m2(
   *(unsigned long long*)(out8 + o) = packed;
 }
 
+// ---- MXFP4: OCP e2m1 codes, one E8M0 scale per 32 consecutive K elements ---
+//
+// The scale bytes of an [R, K] operand (R % 64 == 0, K % 256 == 0) are stored
+// in the order gemm_mx4.hip's K-loop reads them: per (64-row group G, 256-
+// element K-tile t) one 512-byte chunk, lane-major, so a wave fetches the
+// scales of its 64 rows for one K-tile with ONE coalesced 8-byte load per
+// lane.  Lane kg*16+fl owns the 8 bytes [h][i] = scale of row 16*i+fl of the
+// group, 32-block 4*h+kg of the tile: dword h is the scale VGPR of the K=128
+// MFMA h, and the fragment index i is its op_sel byte.
+// ops/reference.py (mxfp4_scale_index) mirrors this rule.
+__device__ __forceinline__ long long mx4_scale_index(long long row, int blk,
+                                                     int nt /* K/256 */) {
+  const long long G = row >> 6;
+  const int r = (int)(row & 63);
+  const int t = blk >> 3, b = blk & 7;
+  return ((G * nt + t) * 64 + (b & 3) * 16 + (r & 15)) * 8 + (b >> 2) * 4 +
+         (r >> 4);
+}
+
+// Block exponent from |amax|'s bit pattern: the smallest e with amax / 2^e
+// <= 6 (= 1.5 * 2^2), clamped to [-127, 127]; 0 for a zero or non-finite
+// amax.  Field arithmetic, so the boundary is exact.
+__device__ __forceinline__ int mx4_block_exponent(unsigned int amax_bits) {
+  const int E = (int)(amax_bits >> 23);
+  const unsigned int man = amax_bits & 0x7FFFFFu;
+  if (amax_bits == 0u || E == 255) return 0;
+  const int e = E - 127 - 2 + (man > 0x400000u ? 1 : 0);
+  return min(max(e, -127), 127);
+}
+
+// 8 values of one thread -> 8 e2m1 codes (one 4-byte store, element 2i in the
+// low nibble of byte i) and, from the first of the four ADJACENT lanes that
+// hold a 32-block, its E8M0 byte.  The block amax is two cross-lane steps
+// over the |value| bit patterns (monotone as unsigned ints; NaN and inf sort
+// on top).  Every lane of such a group of four must be active: callers
+// iterate (row, c8) with c8 fastest and H/8 a multiple of 4.  Values are
+// scaled exactly (ldexpf) and converted at unit scale by the packed RNE
+// convert, which saturates at +-6.
+__device__ __forceinline__ void e1d_store_mxfp4(
+    unsigned char* __restrict__ q, unsigned char* __restrict__ s,
+    long long row, int h8, int c8, const float (&acc)[8]) {
+  unsigned int am = 0u;
+#pragma unroll
+  for (int e = 0; e < 8; ++e)
+    am = max(am, __float_as_uint(acc[e]) & 0x7FFFFFFFu);
+  am = max(am, (unsigned int)__shfl_xor((int)am, 1, 64));
+  am = max(am, (unsigned int)__shfl_xor((int)am, 2, 64));
+  const int e = mx4_block_exponent(am);
+  float v[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) v[k] = ldexpf(acc[k], -e);
+  unsigned int pk = 0u;
+  pk = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(pk, v[0], v[1], 1.0f, 0);
+  pk = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(pk, v[2], v[3], 1.0f, 1);
+  pk = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(pk, v[4], v[5], 1.0f, 2);
+  pk = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(pk, v[6], v[7], 1.0f, 3);
+  *(unsigned int*)(q + ((row * h8 + c8) << 2)) = pk;
+  if ((c8 & 3) == 0)
+    s[mx4_scale_index(row, c8 >> 2, h8 >> 5)] = (unsigned char)(e + 127);
+}
+
 // ---- host side: what the four op wrappers check and compute alike ----------
 struct Expand1dArgs {
   long long n = 0, H = 0;

@@ -663,3 +663,98 @@ def gemm_mx8_nt_fmt_cpu(a8: torch.Tensor, ea, b8: torch.Tensor, eb,
         c = torch.where(unpack_relu_mask(mask.cpu(), c.shape[1]), c,
                         torch.zeros_like(c))
     return c if out_fp32 else c.to(torch.bfloat16)
+
+
+# --------------------------------------------------------------------------
+# MXFP4 oracle (OCP e2m1 codes, one E8M0 scale per 32 consecutive K
+# elements) — CPU semantics for ops/hip/gemm_mx4.hip
+# --------------------------------------------------------------------------
+
+#: code 0..7 -> magnitude; bit 3 of a code is the sign
+E2M1_GRID = np.array([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0])
+
+
+def _mx4_check(R: int, K: int) -> None:
+    if R % 64 or K % 256 or K <= 0:
+        raise RuntimeError(
+            f"mxfp4 requires rows%64==0 and K%256==0 (got {R}x{K})")
+
+
+def mxfp4_scale_index(R: int, K: int) -> torch.Tensor:
+    """int64 ``[R, K/32]``: where the scale byte of (row, 32-block) lives in
+    the flat scale tensor — the order the GEMM's K-loop reads (the rule and
+    its reason are at ``mx4_scale_index`` in ``ops/hip/expand1d.h``)."""
+    _mx4_check(R, K)
+    row = np.arange(R, dtype=np.int64)[:, None]
+    blk = np.arange(K // 32, dtype=np.int64)[None, :]
+    G, r = row >> 6, row & 63
+    t, b = blk >> 3, blk & 7
+    idx = (((G * (K // 256) + t) * 64 + (b & 3) * 16 + (r & 15)) * 8
+           + (b >> 2) * 4 + (r >> 4))
+    return torch.from_numpy(idx)
+
+
+def mxfp4_block_exponent(amax: np.ndarray) -> np.ndarray:
+    """Smallest e with amax / 2^e <= 6, from the fp32 fields (6 = 1.5 * 2^2:
+    e = E - 2 + (mantissa > 0x400000)), clamped to [-127, 127]; 0 for a zero
+    or non-finite amax."""
+    bits = np.asarray(amax, dtype=np.float32).view(np.uint32) & 0x7FFFFFFF
+    E = (bits >> 23).astype(np.int64)
+    e = E - 127 - 2 + ((bits & 0x7FFFFF) > 0x400000)
+    e = np.clip(e, -127, 127)
+    return np.where((bits == 0) | (E == 255), 0, e)
+
+
+def quantize_mxfp4_cpu(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """x ``[R, K]`` (fp32 / bf16, widened to fp32) -> (codes uint8 ``[R,
+    K/2]``, element 2i in the low nibble of byte i; scales uint8 ``[R*K/32]``
+    bytes ``e + 127`` in :func:`mxfp4_scale_index` order).  Elements are
+    ``x / 2^e`` rounded to the nearest grid value, ties to the even code,
+    saturating at +-6; the sign bit is the input's."""
+    R, K = x.shape
+    _mx4_check(R, K)
+    v = x.detach().float().cpu().numpy().reshape(R, K // 32, 32)
+    with np.errstate(invalid="ignore"):
+        amax = np.abs(v).max(axis=2)
+        amax = np.where(np.isnan(v).any(axis=2), np.float32(np.nan), amax)
+    e = mxfp4_block_exponent(amax)
+    mag = np.minimum(np.abs(v.astype(np.float64))
+                     / np.exp2(e.astype(np.float64))[..., None], 6.0)
+    hi_i = np.clip(np.searchsorted(E2M1_GRID, mag), 0, 7)
+    lo_i = np.clip(hi_i - 1, 0, 7)
+    d_lo, d_hi = mag - E2M1_GRID[lo_i], E2M1_GRID[hi_i] - mag
+    code = np.where(d_hi < d_lo, hi_i, lo_i)
+    code = np.where(d_hi == d_lo, np.where(lo_i % 2 == 0, lo_i, hi_i), code)
+    code = np.where(mag == E2M1_GRID[hi_i], hi_i, code)  # exact grid hits
+    code = (code | (np.signbit(v) << 3)).astype(np.uint8).reshape(R, K)
+    q = code[:, 0::2] | (code[:, 1::2] << 4)
+    s = np.zeros(R * K // 32, dtype=np.uint8)
+    s[mxfp4_scale_index(R, K).numpy().reshape(-1)] = (e + 127).reshape(-1)
+    return torch.from_numpy(q), torch.from_numpy(s)
+
+
+def mxfp4_decode_cpu(q: torch.Tensor, s: torch.Tensor, K: int) -> torch.Tensor:
+    """The logical decode: fp32 ``[R, K]`` of codes ``q`` and scales ``s``
+    (scale byte 255 is NaN, as E8M0 defines it)."""
+    qn = q.detach().cpu().numpy().astype(np.uint8)
+    R = qn.shape[0]
+    code = np.empty((R, K), dtype=np.uint8)
+    code[:, 0::2], code[:, 1::2] = qn & 0xF, qn >> 4
+    val = E2M1_GRID[code & 7] * np.where(code & 8, -1.0, 1.0)
+    sb = s.detach().cpu().numpy().astype(np.uint8).reshape(-1)[
+        mxfp4_scale_index(R, K).numpy()].astype(np.float64)
+    scale = np.where(sb == 255, np.nan, np.exp2(sb - 127.0))
+    return torch.from_numpy(
+        (val.reshape(R, K // 32, 32) * scale[..., None]).reshape(R, K)
+        .astype(np.float32))
+
+
+def gemm_mxfp4_nt_cpu(aq, sa, bq, sb, bias=None, relu=False,
+                      out_fp32=False) -> torch.Tensor:
+    K = aq.shape[1] * 2
+    c = mxfp4_decode_cpu(aq, sa, K) @ mxfp4_decode_cpu(bq, sb, K).t()
+    if bias is not None:
+        c = c + bias.detach().cpu().float()
+    if relu:
+        c = torch.relu(c)
+    return c if out_fp32 else c.to(torch.bfloat16)

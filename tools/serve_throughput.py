@@ -6,7 +6,7 @@ per-request and steady-state rows/s plus the server's own /stats.  The
 round-1 linear measurement (129-189M rows/s) came from an inline script;
 this makes it reproducible and adds the MLP bf16/fp8 variants.
 
-    python tools/serve_throughput.py --model linear|mlp|mlp-fp8
+    python tools/serve_throughput.py --model linear|mlp|mlp-fp8|mlp-fp4
 """
 from __future__ import annotations
 
@@ -25,7 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 def main() -> None:
     p = argparse.ArgumentParser()
     p.add_argument("--model", default="linear",
-                   choices=["linear", "mlp", "mlp-fp8"])
+                   choices=["linear", "mlp", "mlp-fp8", "mlp-fp4"])
     p.add_argument("--rows", type=int, default=200_000,
                    help="training rows")
     p.add_argument("--batch", type=int, default=4_000_000)
@@ -34,10 +34,10 @@ def main() -> None:
     p.add_argument("--mlp-steps", type=int, default=10)
     args = p.parse_args()
 
-    if args.model == "mlp-fp8":
-        os.environ["BODYWORK_MLP_FP8"] = "1"
+    if args.model in ("mlp-fp8", "mlp-fp4"):
+        tag = args.model
+        os.environ["BODYWORK_MLP_" + tag[4:].upper()] = "1"
         args.model = "mlp"
-        tag = "mlp-fp8"
     else:
         tag = args.model
 
