@@ -1247,8 +1247,12 @@ def quantize_mxfp4(
     Per block the exponent is the smallest ``e`` with ``amax / 2^e <= 6``
     (from the float fields; 0 for a zero or non-finite block), the elements
     are ``x / 2^e`` rounded to the nearest of 0, 0.5, 1, 1.5, 2, 3, 4, 6,
-    ties to the even code, saturating.  The ORDER of ``s`` is private to
-    these ops (the GEMM's K-loop order); ``reference.mxfp4_decode_cpu`` is
+    ties to the even code, saturating.  In a block that holds an inf or a
+    NaN the finite elements are quantised at ``e = 0``, inf saturates to
+    +-6 and a NaN element becomes code 7 with the NaN's own sign bit (+-6:
+    e2m1 has no NaN; it is what the device's convert emits).  The ORDER of
+    ``s`` is private to these ops (the GEMM's K-loop order);
+    ``reference.mxfp4_decode_cpu`` is
     the logical decode.  Requires R%64==0 and K%256==0.  ``out=(q, s)``
     writes into existing tensors (a hot redeploy keeps its pointers).
     CPU oracle: ``reference.quantize_mxfp4_cpu``."""
@@ -1289,7 +1293,10 @@ def expand1d_mxfp4(
     h = x.float()[:, None] * w.float()[None, :]
     if b is not None:
         h = h + b.float()[None, :]
-    return reference.quantize_mxfp4_cpu(torch.relu(h))
+    # max(-0, +0) is +0 on the device (fmaxf); torch's CPU relu keeps a
+    # negative zero (0 * a negative w, no bias), whose sign the quantiser
+    # would put into the code
+    return reference.quantize_mxfp4_cpu(torch.relu(h) + 0.0)
 
 
 def gemm_mxfp4_nt(
@@ -1307,7 +1314,10 @@ def gemm_mxfp4_nt(
     Runs the fp4 form of the gfx950 scaled MFMA
     (v_mfma_scale_f32_16x16x128_f8f6f4, cbsz = blgp = 4) with true per-block
     scales fetched in the K-loop (ops/hip/gemm_mx4.hip).  Requires
-    M%256==0, N%256==0, K%256==0.  CPU oracle: decode + fp32 matmul."""
+    M%256==0, N%256==0, K%256==0.  Scale bytes 0..254 (2^-127..2^127) are
+    exact on the device, also where one operand's is tiny and the other's
+    huge in one product.  CPU oracle: decode + fp32 matmul (its fp32 decode
+    overflows from 4 * 2^126 up, which the device's operands do not)."""
     if aq.device.type == "cuda":
         core = _core(aq.device)
         return core.gemm_mxfp4_nt(

@@ -72,6 +72,12 @@
 // element 2i in the low nibble; block exponent e = smallest integer with
 // amax / 2^e <= 6, from the float's fields; round to nearest, ties to the
 // even code, saturating at +-6.  C accumulates in fp32 in the MFMA.
+// A block that holds an inf or a NaN has e = 0 and its finite elements are
+// quantised at that e; inf saturates to +-6, and a NaN element becomes code 7
+// with the NaN's own sign bit (+-6, what the packed convert emits for it,
+// whatever its payload; e2m1 has no NaN).  Scale bytes 0..254 are exact
+// through the MFMA, alone and in pairs (2^-127 against 2^127 in one
+// product); byte 255 is NaN and is only ever met on dead rows.
 #include <ATen/cuda/CUDAContext.h>
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>

@@ -673,6 +673,12 @@ def gemm_mx8_nt_fmt_cpu(a8: torch.Tensor, ea, b8: torch.Tensor, eb,
 #: code 0..7 -> magnitude; bit 3 of a code is the sign
 E2M1_GRID = np.array([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0])
 
+#: e2m1 has no NaN.  A NaN element becomes this magnitude code with the NaN's
+#: own sign bit — what gfx950's packed convert emits (measured,
+#: profiles/mx_fp4_scoring.md).  Its block has e = 0 like any non-finite
+#: block, and its 31 neighbours are quantised at e = 0 as if it were absent.
+E2M1_NAN_CODE = 7
+
 
 def _mx4_check(R: int, K: int) -> None:
     if R % 64 or K % 256 or K <= 0:
@@ -710,7 +716,10 @@ def quantize_mxfp4_cpu(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     K/2]``, element 2i in the low nibble of byte i; scales uint8 ``[R*K/32]``
     bytes ``e + 127`` in :func:`mxfp4_scale_index` order).  Elements are
     ``x / 2^e`` rounded to the nearest grid value, ties to the even code,
-    saturating at +-6; the sign bit is the input's."""
+    saturating at +-6; the sign bit is the input's.  A block with an inf or
+    a NaN has ``e = 0``: inf saturates, a NaN element gets
+    :data:`E2M1_NAN_CODE` with its own sign bit, the finite elements are
+    quantised at ``e = 0``."""
     R, K = x.shape
     _mx4_check(R, K)
     v = x.detach().float().cpu().numpy().reshape(R, K // 32, 32)
@@ -718,14 +727,16 @@ def quantize_mxfp4_cpu(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
         amax = np.abs(v).max(axis=2)
         amax = np.where(np.isnan(v).any(axis=2), np.float32(np.nan), amax)
     e = mxfp4_block_exponent(amax)
-    mag = np.minimum(np.abs(v.astype(np.float64))
-                     / np.exp2(e.astype(np.float64))[..., None], 6.0)
+    with np.errstate(invalid="ignore"):  # widening a signalling NaN
+        mag = np.minimum(np.abs(v.astype(np.float64))
+                         / np.exp2(e.astype(np.float64))[..., None], 6.0)
     hi_i = np.clip(np.searchsorted(E2M1_GRID, mag), 0, 7)
     lo_i = np.clip(hi_i - 1, 0, 7)
     d_lo, d_hi = mag - E2M1_GRID[lo_i], E2M1_GRID[hi_i] - mag
     code = np.where(d_hi < d_lo, hi_i, lo_i)
     code = np.where(d_hi == d_lo, np.where(lo_i % 2 == 0, lo_i, hi_i), code)
     code = np.where(mag == E2M1_GRID[hi_i], hi_i, code)  # exact grid hits
+    code = np.where(np.isnan(v), E2M1_NAN_CODE, code)
     code = (code | (np.signbit(v) << 3)).astype(np.uint8).reshape(R, K)
     q = code[:, 0::2] | (code[:, 1::2] << 4)
     s = np.zeros(R * K // 32, dtype=np.uint8)
@@ -733,9 +744,11 @@ def quantize_mxfp4_cpu(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     return torch.from_numpy(q), torch.from_numpy(s)
 
 
-def mxfp4_decode_cpu(q: torch.Tensor, s: torch.Tensor, K: int) -> torch.Tensor:
-    """The logical decode: fp32 ``[R, K]`` of codes ``q`` and scales ``s``
-    (scale byte 255 is NaN, as E8M0 defines it)."""
+def mxfp4_decode_cpu(q: torch.Tensor, s: torch.Tensor, K: int,
+                     dtype=np.float32) -> torch.Tensor:
+    """The logical decode: ``[R, K]`` of codes ``q`` and scales ``s`` (scale
+    byte 255 is NaN, as E8M0 defines it).  fp32 by default, where 4 * 2^126
+    and above overflow to inf; ``dtype=np.float64`` holds every value."""
     qn = q.detach().cpu().numpy().astype(np.uint8)
     R = qn.shape[0]
     code = np.empty((R, K), dtype=np.uint8)
@@ -744,9 +757,10 @@ def mxfp4_decode_cpu(q: torch.Tensor, s: torch.Tensor, K: int) -> torch.Tensor:
     sb = s.detach().cpu().numpy().astype(np.uint8).reshape(-1)[
         mxfp4_scale_index(R, K).numpy()].astype(np.float64)
     scale = np.where(sb == 255, np.nan, np.exp2(sb - 127.0))
-    return torch.from_numpy(
-        (val.reshape(R, K // 32, 32) * scale[..., None]).reshape(R, K)
-        .astype(np.float32))
+    with np.errstate(over="ignore"):
+        return torch.from_numpy(
+            (val.reshape(R, K // 32, 32) * scale[..., None]).reshape(R, K)
+            .astype(dtype))
 
 
 def gemm_mxfp4_nt_cpu(aq, sa, bq, sb, bias=None, relu=False,

@@ -14,6 +14,7 @@ import torch
 
 from bodywork_mlops_demo_amd import ops
 from bodywork_mlops_demo_amd.ops import reference as ref
+from mx4_data import grid_operand
 
 pytestmark = pytest.mark.gpu
 
@@ -21,25 +22,12 @@ DEV = "cuda"
 K = 1024  # smallest K that turns the three-slot rotation fully over
 
 
-def _grid_operand(rows, seed, spread):
-    """(grid value, all 15) x 2^s(row, block), s in {0,1,2}; each block holds
-    a 4 or a 6, so the quantiser must choose e = s."""
-    g = torch.Generator().manual_seed(seed)
-    vals = torch.tensor([0, .5, 1, 1.5, 2, 3, 4, 6, -.5, -1, -1.5, -2, -3,
-                         -4, -6])
-    x = vals[torch.randint(0, 15, (rows, K), generator=g)]
-    x[:, ::32] = torch.tensor([4., -6., 6., -4.])[
-        torch.randint(0, 4, (rows, K // 32), generator=g)]
-    row = torch.arange(rows)[:, None]
-    blk = torch.arange(K // 32)[None, :]
-    s = (row * spread[0] + blk * spread[1] + (row // 16) * (blk // 4)) % 3
-    return x * (2.0 ** s).repeat_interleave(32, dim=1)
-
-
 @functools.lru_cache(maxsize=None)
 def _exact():
-    a = _grid_operand(768, 1, (1, 1)).to(DEV)
-    b = _grid_operand(512, 2, (2, 1)).to(DEV)
+    # the construction lives in tests/mx4_data.py, which takes K; the other
+    # tile counts are in tests/test_mx4_edges_gpu.py
+    a = grid_operand(768, 1, (1, 1), K).to(DEV)
+    b = grid_operand(512, 2, (2, 1), K).to(DEV)
     c = (a.double() @ b.double().t())
     g = torch.Generator().manual_seed(3)
     b2 = torch.randint(-8, 9, (512,), generator=g).float().to(DEV)
@@ -161,6 +149,20 @@ def test_mlp_fp4_scoring_task_parity():
           f"deviation {dev:.5f}")
     assert abs(mape_f4 - mape_bf) < 0.05 * mape_bf + 0.01, (mape_bf, mape_f4)
     assert dev < FP4_PREDICTION_DEVIATION_BOUND, dev
+
+
+def test_mlp_fp4_forward_at_an_odd_tile_count():
+    """hidden = 768 is three K-tiles: the forward reaches the K-loop's third
+    tail phase.  Untrained; only the forward pass is in question."""
+    from bodywork_mlops_demo_amd.models import GPUMLPRegressor
+
+    m = GPUMLPRegressor(hidden=768, device=DEV, seed=5, fp4_scoring=True)
+    g = torch.Generator(device=DEV).manual_seed(14)
+    X = torch.rand(512, generator=g, device=DEV) * 100
+    got = m.predict(X)
+    assert m._w2_q4 is not None  # the fp4 path ran
+    torch.testing.assert_close(got, _head_fp64(m, X)[1], rtol=1e-3,
+                               atol=1e-2)
 
 
 def test_mlp_fp4_scorer_capture_and_hot_redeploy():
