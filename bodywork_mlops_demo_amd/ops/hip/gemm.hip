@@ -22,13 +22,15 @@
 // register-staged kernels pad rows to 72 shorts (144-B stride) instead.
 // fp32 C/D per guide §3: col = lane&15, row = (lane>>4)*4 + reg.
 // The epilogue of a wave's 64x64 block (tile_epilogue, modes Epi::*) is
-// shared with gemm8.hip and gemm_mx8.hip: mfma_tile.h.
+// shared with gemm8.hip, gemm_mx8.hip and gemm_mx4.hip: mfma_tile.h; the
+// runtime -> template epilogue ladder is gemm_host.h's.
 #include <ATen/cuda/CUDAContext.h>
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 
 #include "bf16_utils.h"
-#include "mfma_tile.h"
+#include "gemm_host.h"
+#include "tile256.h"  // zero_acc
 
 #define BM 128
 #define BN 128
@@ -139,10 +141,7 @@ __global__ void gemm_nt_glds_kernel(
   const int swz = fl & 7;  // read-side XOR factor (row & 7 == fl & 7)
 
   f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
   const int TILE = 128 * 64;  // shorts per tile
 
@@ -216,10 +215,7 @@ __global__ void gemm_bf16_kernel(
   const int kg = lane >> 4;       // k-group 0..3 (8 elems each)
 
   f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
   for (long long k0 = 0; k0 < K; k0 += BK) {
     if (TN) {
@@ -266,6 +262,8 @@ static void launch_gemm(bool tn, Epi epi, bool has_bias, bool out_fp32,
   const bf16_t* ap = (const bf16_t*)a.data_ptr();
   const bf16_t* bp = (const bf16_t*)b.data_ptr();
   void* cp = c.data_ptr();
+  TORCH_CHECK(mask_out == nullptr || !out_fp32,
+              "launch_gemm: the mask-emitting kernels write bf16 only");
 
   // deep-pipeline 16-wave 256^2 8-phase kernel (gemm8.hip) for
   // exact-tile shapes — DEFAULT ON: A/B-measured on MI355X at
@@ -292,50 +290,44 @@ static void launch_gemm(bool tn, Epi epi, bool has_bias, bool out_fp32,
   hipLaunchKernelGGL((gemm_nt_glds_kernel<EPI_, HB_, OF_, EM_>), grid,      \
                      dim3(GEMM_THREADS), 0, stream, ap, bp, bias, mask,     \
                      mask_out, cp, M, N, K)
-    if (epi == Epi::BiasRelu && mask_out != nullptr) {
-      if (has_bias) { if (out_fp32) G_GLDS(Epi::BiasRelu, true, true, true);
-                      else          G_GLDS(Epi::BiasRelu, true, false, true); }
-      else          { if (out_fp32) G_GLDS(Epi::BiasRelu, false, true, true);
-                      else          G_GLDS(Epi::BiasRelu, false, false, true); }
-    } else if (epi == Epi::BiasRelu) {
-      if (has_bias) { if (out_fp32) G_GLDS(Epi::BiasRelu, true, true, false);
-                      else          G_GLDS(Epi::BiasRelu, true, false, false); }
-      else          { if (out_fp32) G_GLDS(Epi::BiasRelu, false, true, false);
-                      else          G_GLDS(Epi::BiasRelu, false, false, false); }
+    if (epi == Epi::BiasRelu && mask_out != nullptr) {  // bf16 output only
+      if (has_bias) G_GLDS(Epi::BiasRelu, true, false, true);
+      else          G_GLDS(Epi::BiasRelu, false, false, true);
     } else if (epi == Epi::MaskMul) {
       if (out_fp32) G_GLDS(Epi::MaskMul, false, true, false);
       else          G_GLDS(Epi::MaskMul, false, false, false);
     } else {
-      if (out_fp32) G_GLDS(Epi::None, false, true, false);
-      else          G_GLDS(Epi::None, false, false, false);
+      dispatch_epilogue(epi == Epi::BiasRelu, has_bias, out_fp32,
+                        [&](auto e, auto hb, auto of) {
+                          G_GLDS(decltype(e)::value, decltype(hb)::value,
+                                 decltype(of)::value, false);
+                        });
     }
 #undef G_GLDS
     return;
   }
 
-#define G_LAUNCH(TN_, EPI_, HB_, OF_)                                       \
+  /* mask_out unsupported on the fallback kernel (checked in hosts) */
+  auto fallback = [&](auto tn_tag) {
+    constexpr bool TN_ = decltype(tn_tag)::value;
+#define G_LAUNCH(EPI_, HB_, OF_)                                            \
   hipLaunchKernelGGL((gemm_bf16_kernel<TN_, EPI_, HB_, OF_>), grid,         \
                      dim3(GEMM_THREADS), 0, stream, ap, bp, bias, mask, cp, \
                      M, N, K)
-  /* mask_out unsupported on the fallback kernel (checked in hosts) */
-#define G_EPI(TN_)                                                          \
-  do {                                                                      \
-    if (epi == Epi::BiasRelu) {                                             \
-      if (has_bias) { if (out_fp32) G_LAUNCH(TN_, Epi::BiasRelu, true, true);  \
-                      else          G_LAUNCH(TN_, Epi::BiasRelu, true, false); }\
-      else          { if (out_fp32) G_LAUNCH(TN_, Epi::BiasRelu, false, true); \
-                      else          G_LAUNCH(TN_, Epi::BiasRelu, false, false);}\
-    } else if (epi == Epi::MaskMul) {                                       \
-      if (out_fp32) G_LAUNCH(TN_, Epi::MaskMul, false, true);               \
-      else          G_LAUNCH(TN_, Epi::MaskMul, false, false);              \
-    } else {                                                                \
-      if (out_fp32) G_LAUNCH(TN_, Epi::None, false, true);                  \
-      else          G_LAUNCH(TN_, Epi::None, false, false);                 \
-    }                                                                       \
-  } while (0)
-  if (tn) G_EPI(true); else G_EPI(false);
-#undef G_EPI
+    if (epi == Epi::MaskMul) {
+      if (out_fp32) G_LAUNCH(Epi::MaskMul, false, true);
+      else          G_LAUNCH(Epi::MaskMul, false, false);
+    } else {
+      dispatch_epilogue(epi == Epi::BiasRelu, has_bias, out_fp32,
+                        [&](auto e, auto hb, auto of) {
+                          G_LAUNCH(decltype(e)::value, decltype(hb)::value,
+                                   decltype(of)::value);
+                        });
+    }
 #undef G_LAUNCH
+  };
+  if (tn) fallback(std::true_type{});
+  else    fallback(std::false_type{});
 }
 
 // C = x @ w^T (+bias)(+relu | *mask); x [M,K], w [N,K]

@@ -78,13 +78,18 @@
 // whatever its payload; e2m1 has no NaN).  Scale bytes 0..254 are exact
 // through the MFMA, alone and in pairs (2^-127 against 2^127 in one
 // product); byte 255 is NaN and is only ever met on dead rows.
+//
+// This kernel keeps its own copy of the front end that gemm8.hip and
+// gemm_mx8.hip take from tile256.h: built on that header it allocated 126
+// VGPRs instead of 118 and its scoring head measured 0.6% slower
+// (profiles/gemm_front_end.md).  The host side is gemm_host.h's.
 #include <ATen/cuda/CUDAContext.h>
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 
 #include "bf16_utils.h"
 #include "expand1d.h"
-#include "host_checks.h"
+#include "gemm_host.h"
 #include "mfma_tile.h"
 
 #define M4_BM 256
@@ -377,28 +382,19 @@ void quantize_mxfp4_hip(const at::Tensor& x, at::Tensor q, at::Tensor s) {
   const char* op = "quantize_mxfp4";
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2, op,
               ": x must be a contiguous 2-d cuda tensor");
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 ||
-                  x.scalar_type() == torch::kFloat,
-              op, ": bf16 or fp32 input");
   const long long R = x.size(0), K = x.size(1);
   m4_check_shape(op, R, K);
   m4_check_out(op, x, q, s, R, K);
   TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0, op,
               ": x must be 16-byte aligned");
-  if (R == 0 || K == 0) return;
-  auto stream = at::cuda::getCurrentCUDAStream();
   const int k8 = (int)(K / 8);
-  const int grid = (int)std::min<long long>((R * k8 + 255) / 256, 8192);
-  if (x.scalar_type() == torch::kBFloat16)
-    hipLaunchKernelGGL(quantize_mxfp4_kernel<short>, dim3(grid), dim3(256),
-                       0, stream, (const short*)x.data_ptr(),
+  launch_quantiser(op, x, R * k8, [&](auto* xp, int blocks) {
+    hipLaunchKernelGGL(quantize_mxfp4_kernel<std::decay_t<decltype(*xp)>>,
+                       dim3(blocks), dim3(256), 0,
+                       at::cuda::getCurrentCUDAStream(), xp,
                        q.data_ptr<unsigned char>(),
                        s.data_ptr<unsigned char>(), R, k8);
-  else
-    hipLaunchKernelGGL(quantize_mxfp4_kernel<float>, dim3(grid), dim3(256),
-                       0, stream, x.data_ptr<float>(),
-                       q.data_ptr<unsigned char>(),
-                       s.data_ptr<unsigned char>(), R, k8);
+  });
 }
 
 // n_dev: only the first n_dev rows are computed; the rest of both outputs
@@ -427,72 +423,40 @@ std::tuple<at::Tensor, at::Tensor> expand1d_mxfp4_hip(
   return {q, s};
 }
 
-// Everything a gemm_mxfp4_nt_kernel launch takes.
-struct Mx4Gemm {
-  long long M = 0, N = 0, K = 0;
-  dim3 grid;
-  const unsigned char* a = nullptr;
-  const unsigned char* sa = nullptr;
-  const unsigned char* b = nullptr;
-  const unsigned char* sb = nullptr;
-  const float* bias = nullptr;      // BiasRelu / ReluDot
-  const float* w3 = nullptr;        // ReluDot
-  const int64_t* n_live = nullptr;  // LIVE
-  void* c = nullptr;
-  bool empty() const { return M == 0 || N == 0; }
-};
-
 // The operands every MXFP4 GEMM op takes: codes aq [M, K/2], bq [N, K/2]
-// and their scale tensors.  `op` prefixes the error texts.
-static Mx4Gemm m4_gemm_operands(const char* op, const at::Tensor& aq,
-                                const at::Tensor& as, const at::Tensor& bq,
-                                const at::Tensor& bs) {
-  for (const at::Tensor* t : {&aq, &as, &bq, &bs})
+// (gemm_host.h's check) and their scale tensors.  `op` prefixes the error
+// texts.
+static MxGemm m4_gemm_operands(const char* op, const at::Tensor& aq,
+                               const at::Tensor& as, const at::Tensor& bq,
+                               const at::Tensor& bs) {
+  // k_max: the per-lane staging offset is a 32-bit int
+  static const GemmFormat fp4{torch::kUInt8, "fp4 code byte", 1, 2, M4_BK,
+                              1ll << 24};
+  MxGemm g(gemm256_operands(op, fp4, aq, bq));
+  // the kernel's last phase runs whatever nt is
+  TORCH_CHECK(g.K > 0, op, ": K must be positive");
+  for (const at::Tensor* t : {&as, &bs})
     TORCH_CHECK(t->is_cuda() && t->device() == aq.device() &&
                     t->scalar_type() == torch::kUInt8 && t->is_contiguous(),
-                op, ": codes and scales must be contiguous uint8 cuda "
-                "tensors on one device");
-  TORCH_CHECK(aq.dim() == 2 && bq.dim() == 2 && aq.size(1) == bq.size(1), op,
-              ": [M,K/2]x[N,K/2]");
-  Mx4Gemm g;
-  g.M = aq.size(0), g.K = aq.size(1) * 2, g.N = bq.size(0);
-  TORCH_CHECK(g.M % M4_BM == 0 && g.N % M4_BN == 0 && g.K % M4_BK == 0 &&
-                  g.K > 0,
-              op, " requires M%256==0, N%256==0, K%256==0 (got ", g.M, "x",
-              g.N, "x", g.K, ")");
+                op, ": scales must be contiguous uint8 cuda tensors on the "
+                "codes' device");
   TORCH_CHECK(as.numel() == g.M * g.K / 32 && bs.numel() == g.N * g.K / 32,
               op, ": a scale tensor holds rows*K/32 bytes");
-  // the per-lane staging offset is a 32-bit int
-  TORCH_CHECK(g.K <= (1ll << 24), op, ": K too large");
-  TORCH_CHECK((uintptr_t)aq.data_ptr() % 16 == 0 &&
-                  (uintptr_t)bq.data_ptr() % 16 == 0 &&
-                  (uintptr_t)as.data_ptr() % 8 == 0 &&
+  TORCH_CHECK((uintptr_t)as.data_ptr() % 8 == 0 &&
                   (uintptr_t)bs.data_ptr() % 8 == 0,
-              op, ": codes must be 16-byte and scales 8-byte aligned");
-  g.grid = dim3((unsigned)(g.N / M4_BN), (unsigned)(g.M / M4_BM));
-  g.a = aq.data_ptr<unsigned char>();
-  g.sa = as.data_ptr<unsigned char>();
-  g.b = bq.data_ptr<unsigned char>();
-  g.sb = bs.data_ptr<unsigned char>();
+              op, ": scales must be 8-byte aligned");
+  g.sa_blk = as.data_ptr<unsigned char>();
+  g.sb_blk = bs.data_ptr<unsigned char>();
   return g;
 }
 
-// optional fp32 [N] epilogue vector -> pointer, nullptr when absent
-static const float* m4_vec_n(const char* op, const char* what,
-                             const c10::optional<at::Tensor>& v, long long N) {
-  if (!v.has_value() || !v->defined()) return nullptr;
-  TORCH_CHECK(v->is_cuda() && v->scalar_type() == torch::kFloat &&
-                  v->numel() == N && v->is_contiguous(),
-              op, ": ", what, " must be a contiguous fp32 [N] cuda tensor");
-  return v->data_ptr<float>();
-}
-
 template <Epi EPI, bool HAS_BIAS, bool OUT_FP32, bool LIVE = false>
-static void m4_launch(const Mx4Gemm& g) {
+static void m4_launch(const MxGemm& g) {
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL((gemm_mxfp4_nt_kernel<EPI, HAS_BIAS, OUT_FP32, LIVE>),
-                     g.grid, dim3(M4_THREADS), 0, stream, g.a, g.sa, g.b,
-                     g.sb, g.bias, g.w3, g.c, g.M, g.N, g.K, g.n_live);
+                     g.grid(), dim3(M4_THREADS), 0, stream, g.a8(),
+                     g.sa_blk, g.b8(), g.sb_blk, g.bias, g.w3, g.c, g.M, g.N,
+                     g.K, g.n_live);
 }
 
 // C[M,N] = A[M,K] . B[N,K]^T over MXFP4 operands, optional fused bias+relu
@@ -502,23 +466,18 @@ at::Tensor gemm_mxfp4_nt_hip(const at::Tensor& aq, const at::Tensor& as,
                              const c10::optional<at::Tensor>& bias, bool relu,
                              bool out_fp32) {
   const char* op = "gemm_mxfp4_nt";
-  Mx4Gemm g = m4_gemm_operands(op, aq, as, bq, bs);
-  g.bias = m4_vec_n(op, "bias", bias, g.N);
+  MxGemm g = m4_gemm_operands(op, aq, as, bq, bs);
+  g.bias = epi_vec_n(op, "bias", bias, g.N);
   TORCH_CHECK(relu || !g.bias, op, ": bias requires the relu epilogue");
   auto opts = aq.options().dtype(out_fp32 ? torch::kFloat : torch::kBFloat16);
   auto C = torch::empty({g.M, g.N}, opts);
   if (g.empty()) return C;
   g.c = C.data_ptr();
-  if (!relu) {
-    if (out_fp32) m4_launch<Epi::None, false, true>(g);
-    else          m4_launch<Epi::None, false, false>(g);
-  } else if (g.bias) {
-    if (out_fp32) m4_launch<Epi::BiasRelu, true, true>(g);
-    else          m4_launch<Epi::BiasRelu, true, false>(g);
-  } else {
-    if (out_fp32) m4_launch<Epi::BiasRelu, false, true>(g);
-    else          m4_launch<Epi::BiasRelu, false, false>(g);
-  }
+  dispatch_epilogue(relu, g.bias != nullptr, out_fp32,
+                    [&](auto e, auto hb, auto of) {
+                      m4_launch<decltype(e)::value, decltype(hb)::value,
+                                decltype(of)::value>(g);
+                    });
   return C;
 }
 
@@ -530,9 +489,9 @@ at::Tensor gemm_mxfp4_relu_dot_hip(const at::Tensor& aq, const at::Tensor& as,
                                    const at::Tensor& b2, const at::Tensor& w3,
                                    const c10::optional<at::Tensor>& n_dev) {
   const char* op = "gemm_mxfp4_relu_dot";
-  Mx4Gemm g = m4_gemm_operands(op, aq, as, bq, bs);
-  g.bias = m4_vec_n(op, "b2", b2, g.N);
-  g.w3 = m4_vec_n(op, "w3", w3, g.N);
+  MxGemm g = m4_gemm_operands(op, aq, as, bq, bs);
+  g.bias = epi_vec_n(op, "b2", b2, g.N);
+  g.w3 = epi_vec_n(op, "w3", w3, g.N);
   TORCH_CHECK(g.bias && g.w3, op, ": b2 and w3 are required");
   g.n_live = n_live_ptr(n_dev, aq, op);
   auto y = torch::zeros({g.M}, aq.options().dtype(torch::kFloat));

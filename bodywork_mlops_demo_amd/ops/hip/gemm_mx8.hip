@@ -19,6 +19,9 @@
 // MFMA per output fragment (vs four K=32 bf16 MFMAs); each lane's A/B
 // fragment is 32 consecutive k bytes (two adjacent ds_read_b128).
 //
+// Coordinates, live-row preamble, stager, prologue and the landing wait are
+// tile256.h's.
+//
 // Schedule: A is double-buffered, B TRIPLE-buffered (LDS = 2x32 + 3x32 =
 // 160 KB, the full CU), which is what lets one barrier per K-tile keep
 // every overwrite barrier-separated.  Per tile T (slots: A T%2, B T%3):
@@ -28,12 +31,9 @@
 //   issue B(T+2) -> slot (T+2)%3   [overwrites B(T-1), read last phase]
 //   read B(T) x4 frags + A mfrag 0,1; 8 MFMAs; read A mfrag 2,3; 8 MFMAs
 //
-// Landing proof: per phase the issue order is [A(T+1), B(T+2)], so at
-// wait(T) the 2 newest outstanding glds are B(T+1)'s halves (issued at
-// phase T-1 after A(T)) — vmcnt(2) proves A(T) and everything older
-// (incl. B(T), issued at phase T-2) landed.  Near the end the guarded
-// issues only SHRINK the outstanding set, and the final tile waits
-// vmcnt(0).  Slot safety: both overwrites target buffers whose reads
+// Landing: per phase the issue order is [A(T+1), B(T+2)], which is all
+// tile256.h's proof asks; near the end the guarded issues only SHRINK the
+// outstanding set.  Slot safety: both overwrites target buffers whose reads
 // were consumed by the PREVIOUS phase's MFMAs, before this phase's
 // barrier.
 //
@@ -66,14 +66,11 @@
 
 #include "bf16_utils.h"
 #include "expand1d.h"
-#include "host_checks.h"
-#include "mfma_tile.h"
+#include "gemm_host.h"
+#include "tile256.h"
 
-#define MX_BM 256
-#define MX_BN 256
 #define MX_BK 128           // fp8 elements per K-tile (128 bytes/row)
-#define MX_THREADS 1024
-#define MX_HTB (128 * 128)  // bytes per half-tile slot
+#define MX_HTB T256_HALF_BYTES
 
 typedef __attribute__((ext_vector_type(8))) int mx_i32x8;
 typedef __attribute__((ext_vector_type(4))) int mx_i32x4;
@@ -95,15 +92,6 @@ __device__ __forceinline__ void mx_dev_scales(int& sa, int& sb,
     sa = min(max(sa, 0), 254);
     sb = min(max(sb, 0), 254);
   }
-}
-
-// stage one [128 rows][128 B] half-tile: 1024 16-B chunks, 1024 threads
-// -> ONE wave-level glds per wave (identical to gemm8's g8_stage_half).
-__device__ __forceinline__ void mx_stage_half(char* __restrict__ slot,
-                                              const char* __restrict__ base,
-                                              int off0) {
-  const int wave = threadIdx.x >> 6;
-  glds16(base + off0, slot + wave * 1024);
 }
 
 // ---- per-tensor e4m3 quantisation ----------------------------------------
@@ -151,7 +139,7 @@ __global__ void quantize_e4m3_kernel(const T* __restrict__ x,
 template <Epi EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false,
           int AFMT = MX_FMT_E4M3, int BFMT = MX_FMT_E4M3,
           bool DEV_SCALE = false, bool LIVE = false>
-__launch_bounds__(MX_THREADS)
+__launch_bounds__(T256_THREADS)
 __global__ void gemm_mx8_nt_1p_kernel(
     const unsigned char* __restrict__ A, const unsigned char* __restrict__ B,
     const float* __restrict__ bias, const float* __restrict__ w3,
@@ -163,19 +151,11 @@ __global__ void gemm_mx8_nt_1p_kernel(
     const int64_t* __restrict__ n_live = nullptr) {       // LIVE only
   __shared__ char lds[10 * MX_HTB];  // A 2 slots + B 3 slots, 160 KB
   mx_dev_scales<DEV_SCALE>(sa, sb, ea_dev, eb_dev);
-  const long long m0 = (long long)blockIdx.y * MX_BM;
-  int live_rows = MX_BM;
-  if constexpr (LIVE) {
-    static_assert(EPI == Epi::ReluDot, "live rows: scoring head only");
-    if (!tile_live_rows<MX_BM>(n_live, M, m0, live_rows)) return;
-  }
-  const long long n0 = (long long)blockIdx.x * MX_BN;
-  const int wave = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const int wm = wave >> 2;
-  const int wn = wave & 3;
-  const int fl = lane & 15;
-  const int kg = lane >> 4;
+  int live_rows;
+  if (!tile256_live<EPI, LIVE>(n_live, M, live_rows)) return;
+  const Tile256 tc = tile256_coords();
+  const long long m0 = tc.m0, n0 = tc.n0;
+  const int wm = tc.wm, wn = tc.wn, fl = tc.fl, kg = tc.kg;
   // XOR swizzle at 32-BYTE granularity — the fp8 fragment size, so a
   // fragment is two ADJACENT b128 reads (chunk32 c of row r lives at
   // (c ^ (r & 3)) * 32).  Measured equivalent to the 16-B-chunk
@@ -190,10 +170,7 @@ __global__ void gemm_mx8_nt_1p_kernel(
   const int b_inhalf = (wn & 1) * 64;
 
   f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
   // slot indices only affect LDS ADDRESSES (never register-array
   // indices), so the A slots swap and the B slots rotate as plain
@@ -237,20 +214,9 @@ __global__ void gemm_mx8_nt_1p_kernel(
     int c32 = ((ci & 7) >> 1) ^ (row & 3);
     stg_off = (int)(row * K + (c32 * 32 + (ci & 1) * 16));
   }
-  const char* Ah0 = (const char*)(A + m0 * K);
-  const char* Ah1 = (const char*)(A + (m0 + 128) * K);
-  const char* Bh0 = (const char*)(B + n0 * K);
-  const char* Bh1 = (const char*)(B + (n0 + 128) * K);
+  const Tile256Src src = tile256_src(A, B, m0, n0, K);
 
-  // prologue: A(0), B(0), B(1)
-  mx_stage_half(aw_cur, Ah0, stg_off);
-  mx_stage_half(aw_cur + MX_HTB, Ah1, stg_off);
-  mx_stage_half(bw0, Bh0, stg_off);
-  mx_stage_half(bw0 + MX_HTB, Bh1, stg_off);
-  if (nt > 1) {
-    mx_stage_half(bw1, Bh0 + MX_KOFF(1), stg_off);
-    mx_stage_half(bw1 + MX_HTB, Bh1 + MX_KOFF(1), stg_off);
-  }
+  tile256_prologue(aw_cur, bw0, bw1, src, stg_off, MX_KOFF(1), nt > 1);
 
 #define P1_MFMA(acc_i, afrag)                                               \
   _Pragma("unroll") for (int nf = 0; nf < 4; ++nf)                          \
@@ -258,18 +224,15 @@ __global__ void gemm_mx8_nt_1p_kernel(
           afrag, b_t[nf], acc[acc_i][nf], AFMT, BFMT, 0, sa, 0, sb)
 
   for (int t = 0; t < nt; ++t) {
-    if (t + 1 < nt)
-      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    tile256_wait_landed(t + 1 < nt);
     __builtin_amdgcn_s_barrier();
     if (t + 1 < nt) {
-      mx_stage_half(aw_nxt, Ah0 + MX_KOFF(t + 1), stg_off);
-      mx_stage_half(aw_nxt + MX_HTB, Ah1 + MX_KOFF(t + 1), stg_off);
+      tile256_stage_half(aw_nxt, src.a0 + MX_KOFF(t + 1), stg_off);
+      tile256_stage_half(aw_nxt + MX_HTB, src.a1 + MX_KOFF(t + 1), stg_off);
     }
     if (t + 2 < nt) {
-      mx_stage_half(bw2, Bh0 + MX_KOFF(t + 2), stg_off);
-      mx_stage_half(bw2 + MX_HTB, Bh1 + MX_KOFF(t + 2), stg_off);
+      tile256_stage_half(bw2, src.b0 + MX_KOFF(t + 2), stg_off);
+      tile256_stage_half(bw2 + MX_HTB, src.b1 + MX_KOFF(t + 2), stg_off);
     }
     {
       const char* br = P1_BR_BASE(bw0);
@@ -572,76 +535,26 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> expand1d_bf16_e4m3_hip(
 
 at::Tensor quantize_e4m3_hip(const at::Tensor& x, int64_t e) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous(), "quantize_e4m3: cuda contig");
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 ||
-                  torch::kFloat == x.scalar_type(),
-              "quantize_e4m3: bf16 or fp32 input");
   auto out = torch::empty_like(x, x.options().dtype(torch::kUInt8));
-  long long n = x.numel();
-  if (n == 0) return out;
-  float inv_scale = ldexpf(1.0f, (int)-e);
-  auto stream = at::cuda::getCurrentCUDAStream();
-  long long pairs = (n + 1) / 2;
-  int threads = 256;
-  int blocks = (int)std::min<long long>((pairs + threads - 1) / threads,
-                                        8192);
-  if (x.scalar_type() == torch::kBFloat16)
-    hipLaunchKernelGGL(quantize_e4m3_kernel<short>, dim3(blocks),
-                       dim3(threads), 0, stream,
-                       (const short*)x.data_ptr(),
+  const long long n = x.numel();
+  const float inv_scale = ldexpf(1.0f, (int)-e);
+  launch_quantiser("quantize_e4m3", x, (n + 1) / 2, [&](auto* xp, int blocks) {
+    hipLaunchKernelGGL(quantize_e4m3_kernel<std::decay_t<decltype(*xp)>>,
+                       dim3(blocks), dim3(256), 0,
+                       at::cuda::getCurrentCUDAStream(), xp,
                        out.data_ptr<unsigned char>(), n, inv_scale);
-  else
-    hipLaunchKernelGGL(quantize_e4m3_kernel<float>, dim3(blocks),
-                       dim3(threads), 0, stream, x.data_ptr<float>(),
-                       out.data_ptr<unsigned char>(), n, inv_scale);
+  });
   return out;
 }
 
-// ---- MX GEMM ops: one operand check, one launcher --------------------------
-
-// Everything a gemm_mx8_nt_1p_kernel launch takes.  mx_gemm_operands
-// fills the problem and the operand pointers; each op sets the scales and
-// the epilogue pointers it uses and leaves the rest null.
-struct MxGemm {
-  long long M = 0, N = 0, K = 0;
-  dim3 grid;
-  const unsigned char* a = nullptr;
-  const unsigned char* b = nullptr;
-  int sa = 127, sb = 127;             // E8M0 bytes (host part)
-  const int* ea_dev = nullptr;        // DEV_SCALE
-  const int* eb_dev = nullptr;
-  const float* bias = nullptr;        // BIAS_RELU / RELU_DOT
-  const float* w3 = nullptr;          // RELU_DOT
-  unsigned char* mask_out = nullptr;  // EMIT_MASK
-  const unsigned char* mask_in = nullptr;  // MASK_MUL
-  const int64_t* n_live = nullptr;         // LIVE
-  void* c = nullptr;
-  bool empty() const { return M == 0 || N == 0; }  // nothing to launch
-};
+// ---- MX GEMM ops: gemm_host.h's operand check and launch record -----------
 
 // The operand pair every MX GEMM op takes: a8 [M,K] and b8 [N,K] fp8
 // bytes.  `op` prefixes the error texts.
 static MxGemm mx_gemm_operands(const char* op, const at::Tensor& a8,
                                const at::Tensor& b8) {
-  TORCH_CHECK(a8.is_cuda() && b8.is_cuda(), op, ": cuda tensors");
-  TORCH_CHECK(a8.scalar_type() == torch::kUInt8 &&
-                  b8.scalar_type() == torch::kUInt8,
-              op, ": fp8 byte tensors");
-  TORCH_CHECK(a8.dim() == 2 && b8.dim() == 2 && a8.size(1) == b8.size(1),
-              op, ": [M,K]x[N,K]");
-  TORCH_CHECK(a8.is_contiguous() && b8.is_contiguous(), op,
-              ": operands must be contiguous");
-  MxGemm g;
-  g.M = a8.size(0), g.K = a8.size(1), g.N = b8.size(0);
-  TORCH_CHECK(g.M % MX_BM == 0 && g.N % MX_BN == 0 && g.K % MX_BK == 0, op,
-              " requires M%256==0, N%256==0, K%128==0 (got ", g.M, "x", g.N,
-              "x", g.K, ")");
-  TORCH_CHECK((uintptr_t)a8.data_ptr() % 16 == 0 &&
-                  (uintptr_t)b8.data_ptr() % 16 == 0,
-              op, ": operands must be 16-byte aligned");
-  g.grid = dim3((unsigned)(g.N / MX_BN), (unsigned)(g.M / MX_BM));
-  g.a = a8.data_ptr<unsigned char>();
-  g.b = b8.data_ptr<unsigned char>();
-  return g;
+  static const GemmFormat fp8{torch::kUInt8, "fp8 byte", 1, 1, MX_BK, 0};
+  return MxGemm(gemm256_operands(op, fp8, a8, b8));
 }
 
 // host exponent -> E8M0 byte; out-of-range stays loud
@@ -651,18 +564,6 @@ static int mx_e8m0(const char* op, int64_t e) {
   return (int)e + 127;
 }
 
-// optional fp32 [N] epilogue vector (bias, b2, w3) -> pointer, nullptr
-// when absent
-static const float* mx_vec_n(const char* op, const char* what,
-                             const c10::optional<at::Tensor>& v,
-                             long long N) {
-  if (!v.has_value() || !v->defined()) return nullptr;
-  TORCH_CHECK(v->is_cuda() && v->scalar_type() == torch::kFloat &&
-                  v->numel() == N && v->is_contiguous(),
-              op, ": ", what, " must be a contiguous fp32 [N] cuda tensor");
-  return v->data_ptr<float>();
-}
-
 template <Epi EPI, bool HAS_BIAS, bool OUT_FP32, bool EMIT_MASK = false,
           int AFMT = MX_FMT_E4M3, int BFMT = MX_FMT_E4M3,
           bool DEV_SCALE = false, bool LIVE = false>
@@ -670,8 +571,8 @@ static void mx_launch(const MxGemm& g) {
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL((gemm_mx8_nt_1p_kernel<EPI, HAS_BIAS, OUT_FP32, EMIT_MASK,
                                             AFMT, BFMT, DEV_SCALE, LIVE>),
-                     g.grid, dim3(MX_THREADS), 0, stream, g.a, g.b, g.bias,
-                     g.w3, g.mask_out, g.c, g.M, g.N, g.K, g.sa, g.sb,
+                     g.grid(), dim3(T256_THREADS), 0, stream, g.a8(), g.b8(),
+                     g.bias, g.w3, g.mask_out, g.c, g.M, g.N, g.K, g.sa, g.sb,
                      g.ea_dev, g.eb_dev, g.mask_in, g.n_live);
 }
 
@@ -685,22 +586,17 @@ at::Tensor gemm_mx8_nt_hip(const at::Tensor& a8, int64_t ea,
   MxGemm g = mx_gemm_operands(op, a8, b8);
   g.sa = mx_e8m0(op, ea);
   g.sb = mx_e8m0(op, eb);
-  g.bias = mx_vec_n(op, "bias", bias, g.N);
+  g.bias = epi_vec_n(op, "bias", bias, g.N);
   TORCH_CHECK(relu || !g.bias, op, ": bias requires relu epilogue for now");
   auto opts = a8.options().dtype(out_fp32 ? torch::kFloat : torch::kBFloat16);
   auto C = torch::empty({g.M, g.N}, opts);
   if (g.empty()) return C;
   g.c = C.data_ptr();
-  if (!relu) {
-    if (out_fp32) mx_launch<Epi::None, false, true>(g);
-    else          mx_launch<Epi::None, false, false>(g);
-  } else if (g.bias) {
-    if (out_fp32) mx_launch<Epi::BiasRelu, true, true>(g);
-    else          mx_launch<Epi::BiasRelu, true, false>(g);
-  } else {
-    if (out_fp32) mx_launch<Epi::BiasRelu, false, true>(g);
-    else          mx_launch<Epi::BiasRelu, false, false>(g);
-  }
+  dispatch_epilogue(relu, g.bias != nullptr, out_fp32,
+                    [&](auto e, auto hb, auto of) {
+                      mx_launch<decltype(e)::value, decltype(hb)::value,
+                                decltype(of)::value>(g);
+                    });
   return C;
 }
 
@@ -716,8 +612,8 @@ at::Tensor gemm_mx8_relu_dot_hip(const at::Tensor& a8, int64_t ea,
   MxGemm g = mx_gemm_operands(op, a8, b8);
   g.sa = mx_e8m0(op, ea);
   g.sb = mx_e8m0(op, eb);
-  g.bias = mx_vec_n(op, "b2", b2, g.N);
-  g.w3 = mx_vec_n(op, "w3", w3, g.N);
+  g.bias = epi_vec_n(op, "b2", b2, g.N);
+  g.w3 = epi_vec_n(op, "w3", w3, g.N);
   TORCH_CHECK(g.bias && g.w3, op, ": b2 and w3 are required");
   g.n_live = n_live_ptr(n_dev, a8, op);
   auto y = torch::zeros({g.M}, a8.options().dtype(torch::kFloat));
@@ -742,7 +638,7 @@ std::tuple<at::Tensor, at::Tensor> gemm_mx8_relu_mask_hip(
   MxGemm g = mx_gemm_operands(op, a8, b8);
   g.sa = mx_e8m0(op, ea);
   g.sb = mx_e8m0(op, eb);
-  g.bias = mx_vec_n(op, "bias", bias, g.N);
+  g.bias = epi_vec_n(op, "bias", bias, g.N);
   auto C = torch::empty({g.M, g.N}, a8.options().dtype(torch::kBFloat16));
   auto mask = torch::empty({g.M, g.N / 8}, a8.options());
   if (g.empty()) return {C, mask};
@@ -785,27 +681,16 @@ at::Tensor amax_exponent_e5m2_hip(const at::Tensor& x, const at::Tensor& w) {
 at::Tensor quantize_e5m2_hip(const at::Tensor& x, int64_t e,
                              const c10::optional<at::Tensor>& e_dev) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous(), "quantize_e5m2: cuda contig");
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 ||
-                  x.scalar_type() == torch::kFloat,
-              "quantize_e5m2: bf16 or fp32 input");
   TORCH_CHECK(-127 <= e && e <= 127, "quantize_e5m2: exponent out of range");
   const int* edp = mx_edev_ptr(e_dev, x, "quantize_e5m2");
   auto out = torch::empty_like(x, x.options().dtype(torch::kUInt8));
-  long long n = x.numel();
-  if (n == 0) return out;
-  auto stream = at::cuda::getCurrentCUDAStream();
-  long long pairs = (n + 1) / 2;
-  int threads = 256;
-  int blocks = (int)std::min<long long>((pairs + threads - 1) / threads,
-                                        8192);
-  if (x.scalar_type() == torch::kBFloat16)
-    hipLaunchKernelGGL(quantize_e5m2_kernel<short>, dim3(blocks),
-                       dim3(threads), 0, stream, (const short*)x.data_ptr(),
+  const long long n = x.numel();
+  launch_quantiser("quantize_e5m2", x, (n + 1) / 2, [&](auto* xp, int blocks) {
+    hipLaunchKernelGGL(quantize_e5m2_kernel<std::decay_t<decltype(*xp)>>,
+                       dim3(blocks), dim3(256), 0,
+                       at::cuda::getCurrentCUDAStream(), xp,
                        out.data_ptr<unsigned char>(), n, (int)e, edp);
-  else
-    hipLaunchKernelGGL(quantize_e5m2_kernel<float>, dim3(blocks),
-                       dim3(threads), 0, stream, x.data_ptr<float>(),
-                       out.data_ptr<unsigned char>(), n, (int)e, edp);
+  });
   return out;
 }
 

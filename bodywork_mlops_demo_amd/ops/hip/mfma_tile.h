@@ -1,7 +1,8 @@
-// What the MFMA GEMM kernels (gemm.hip, gemm8.hip, gemm_mx8.hip) share
-// outside their K-loops: the epilogue of one wave's 64x64 block of C, the
-// 16-byte global->LDS load and the accumulator type (the live-row tile test
-// is in live_rows.h).
+// What the MFMA GEMM kernels (gemm.hip, gemm8.hip, gemm_mx8.hip,
+// gemm_mx4.hip) share after their K-loops: the epilogue of one wave's 64x64
+// block of C, plus the 16-byte global->LDS load and the accumulator type.
+// The live-row tile test is in live_rows.h, the front end of the three
+// 256x256-tile kernels in tile256.h, the host side in gemm_host.h.
 //
 // Every kernel gives a wave a 64x64 block = 4x4 fragments of 16x16, fp32
 // C/D layout col = lane&15 (fl), row = (lane>>4)*4 + reg (kg = lane>>4);
@@ -21,12 +22,6 @@ enum class Epi {
   MaskMul,   // multiply by a 1-bit ReLU mask (the ReLU backward)
   ReluDot,   // y[row] += sum_col relu(acc + bias[col]) * w3[col]
 };
-
-// gemm8.hip's launcher, called from gemm.hip's dispatch
-void launch_gemm8(Epi epi, bool has_bias, bool out_fp32, bool emit_mask,
-                  const void* ap, const void* bp, const float* bias,
-                  const unsigned char* mask, unsigned char* mask_out,
-                  void* cp, long long M, long long N, long long K);
 
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
   __builtin_amdgcn_global_load_lds(

@@ -29,6 +29,39 @@ def test_mx8_exact_integer_layout():
     assert torch.equal(got, a @ b.t())
 
 
+@pytest.mark.parametrize("K", [128, 256, 384, 640])
+def test_mx8_k_loop_tails_exact(K):
+    """nt = K/128 = 1, 2, 3, 5 K-tiles: the prologue alone, the prologue's
+    second B tile, and the loop's guarded issues near the end.  Integers in
+    [-8, 8] at exponent 0: every partial sum is an integer of magnitude
+    <= 64*640 = 40960 < 2^24, so fp32 is exact in any order."""
+    a = _randint(256, K, 60 + K)
+    b = _randint(512, K, 61 + K)
+    got = ops.gemm_mx8_nt(ops.quantize_e4m3(a, 0), 0,
+                          ops.quantize_e4m3(b, 0), 0, out_fp32=True)
+    assert torch.equal(got, a @ b.t())
+
+
+def test_mx8_relu_dot_one_k_tile_live_rows():
+    """The fused head at nt = 1 with a live count of 130 in a 256-row tile:
+    rows below the count equal the fp64 head, rows past it are exactly 0."""
+    M, N, K, live = 256, 512, 128, 130
+    a, b = _randint(M, K, 71), _randint(N, K, 72)
+    g = torch.Generator(device=DEV).manual_seed(73)
+    b2 = torch.randint(-4, 5, (N,), generator=g, device=DEV).float()
+    w3 = torch.randint(-4, 5, (N,), generator=g, device=DEV).float()
+    h2 = torch.relu(a.double() @ b.double().t() + b2.double())
+    # every partial sum of a row, in any order, is an integer below 2^24
+    assert (h2 * w3.double().abs()).sum(dim=1).max().item() < 2 ** 24
+    want = h2 @ w3.double()
+    n_dev = torch.tensor([live], dtype=torch.int64, device=DEV)
+    y = ops.gemm_mx8_relu_dot(ops.quantize_e4m3(a, 0), 0,
+                              ops.quantize_e4m3(b, 0), 0, b2, w3, n_dev=n_dev)
+    assert torch.equal(y[:live].double(), want[:live])
+    assert want[:live].abs().max().item() > 0
+    assert (y[live:] == 0).all()
+
+
 def test_mx8_scale_operands_exact():
     a = _randint(256, 1024, 3)
     b = _randint(256, 1024, 4)
@@ -237,6 +270,24 @@ def test_mx8_three_row_blocks_exact():
     y = ops.gemm_mx8_relu_dot(ops.quantize_e4m3(a, 0), 0,
                               ops.quantize_e4m3(b, 0), 0, b2, w3)
     assert torch.equal(y, torch.relu(a @ b.t() + b2) @ w3)
+
+
+def test_bf16_fused_head_rejects_bad_epilogue_vectors():
+    """The fused bf16 head checks b2 / w3 like the MX heads do: a w3 that is
+    not contiguous (handed to the extension as it is; the Python wrapper
+    would copy it) and a b2 of the wrong length both raise."""
+    core = ops._core(torch.device(DEV))
+    x = torch.zeros(256, 256, device=DEV).bfloat16()
+    w = torch.zeros(256, 256, device=DEV).bfloat16()
+    b2 = torch.zeros(256, device=DEV)
+    w3 = torch.zeros(512, device=DEV)[::2]
+    assert w3.numel() == 256 and not w3.is_contiguous()
+    with pytest.raises(RuntimeError):
+        core.gemm8_relu_dot_bf16(x, w, b2, w3, None)
+    with pytest.raises(RuntimeError):
+        ops.linear_relu_dot_bf16(x, w, b2[:255], w3)
+    assert torch.equal(ops.linear_relu_dot_bf16(x, w, b2, w3),
+                       torch.zeros(256, device=DEV))
 
 
 def test_bf16_fused_head_matches_unfused():
