@@ -27,6 +27,14 @@ byte-transposed e4m3 ``h1`` of the forward with the byte-transposed
 Opt-in scoring (``fp4_scoring=True`` / ``BODYWORK_MLP_FP4=1``): layer 1
 and the h2 GEMM + head run on MXFP4 operands (e2m1 codes, per-32-element
 block scales held in device tensors).
+Opt-in skinny scoring (``skinny_scoring=True`` / ``BODYWORK_MLP_SKINNY=1``):
+a batch of at most 64 rows (an online request: the scorer's 1- and 16-row
+buckets) runs the whole forward in ONE kernel, ``ops.mlp_skinny_score``,
+which streams ``W2w_bf`` once across H/16 workgroups and keeps layer 1 and
+the head in registers, instead of the five launches of the unfused path.
+It reads the persistent bf16/fp32 tensors, so a captured bucket follows a
+hot redeploy; a live row count zeroes the rows past it but saves no
+weight traffic.
 
 Artefact: a *real sklearn ``MLPRegressor``* with ``coefs_``/``intercepts_``
 injected, so ``joblib.load`` + ``predict`` work with stock sklearn
@@ -73,7 +81,8 @@ class GPUMLPRegressor:
                  fp8_scoring: bool | None = None,
                  fp8_training: bool | None = None,
                  fp8_backward: bool | None = None,
-                 fp4_scoring: bool | None = None):
+                 fp4_scoring: bool | None = None,
+                 skinny_scoring: bool | None = None):
         self.hidden = hidden
         self.device = canonical_device(device)
         # opt-in MX-fp8 scoring forward (2x-rate K=128 scaled MFMA for the
@@ -94,6 +103,10 @@ class GPUMLPRegressor:
             fp4_scoring = _os_environ_flag("BODYWORK_MLP_FP4")
         self.fp4_scoring = fp4_scoring
         self._w2_q4: tuple[torch.Tensor, torch.Tensor] | None = None
+        # opt-in one-kernel forward for batches of at most 64 rows
+        if skinny_scoring is None:
+            skinny_scoring = _os_environ_flag("BODYWORK_MLP_SKINNY")
+        self.skinny_scoring = skinny_scoring
         # opt-in MX-fp8 TRAINING forward: the h2 = relu(h1 @ W2 + b2) GEMM
         # runs on e4m3 operands (with this flag alone the two backward
         # GEMMs stay bf16 and the gradients pass straight through the
@@ -318,11 +331,18 @@ class GPUMLPRegressor:
         their 1-bit activation masks (consumed by the masked backward —
         16x less mask traffic than re-reading the activations).
 
-        ``n_dev`` (scoring only; see :meth:`predict`) reaches the two
-        tile-gated scoring branches, whose kernels stop at that row; every
-        other branch ignores it and computes all rows."""
+        ``n_dev`` (scoring only; see :meth:`predict`) reaches the skinny
+        branch and the tile-gated scoring branches, whose kernels stop at
+        that row; every other branch ignores it and computes all rows."""
         if want_masks and n_dev is not None:
             raise ValueError("the training forward takes no live row count")
+        if not want_masks and self._use_skinny(x.shape[0]):
+            # the whole forward in one kernel, from raw x (the kernel
+            # standardises it); never overlaps the tile-gated branches below
+            yhat = ops.mlp_skinny_score(
+                x, self.X_MU, self.X_SIGMA, self.w1_bf, self.b1_bf,
+                self.W2w_bf, self.b2, self.w3, self.b3, n_dev=n_dev)
+            return yhat, None, None, None, None, None
         xn = (x.float() - self.X_MU) / self.X_SIGMA
         if want_masks and self._use_fp8_train(xn.shape[0]):
             # fp8 training forward: dual-emit layer 1 (bf16 + mask for the
@@ -382,6 +402,15 @@ class GPUMLPRegressor:
         yhat = ops.rowdot_bf16(h2, self.w3_bf, self.b3)
         return yhat, h1, h2, xn, m1, m2
 
+    #: largest batch of the one-kernel forward (ops/hip/mlp_skinny.hip)
+    SKINNY_MAX_ROWS = 64
+
+    def _use_skinny(self, m: int) -> bool:
+        """One-kernel skinny forward: opt-in, GPU-only, 1..64 rows."""
+        return (self.skinny_scoring and self.device.type == "cuda"
+                and 1 <= m <= self.SKINNY_MAX_ROWS
+                and self.hidden % 256 == 0)
+
     def _use_fp8(self, m: int) -> bool:
         """MX-fp8 scoring is opt-in, GPU-only, and tile-shape-gated
         (the K=128 scaled-MFMA kernel serves M%256==0; other batch sizes
@@ -419,8 +448,10 @@ class GPUMLPRegressor:
         is a live row count that the kernels read at run time: rows
         ``< n_dev`` of the result are right, the rest unspecified.  On the
         GPU, batches of a multiple of 256 rows skip the work past the
-        count (row tiles of the fused head return at once); other batch
-        sizes, and the CPU, ignore it and compute every row."""
+        count (row tiles of the fused head return at once); with
+        ``skinny_scoring`` batches of at most 64 rows honour it too (rows
+        past it come out as 0); other batch sizes, and the CPU, ignore it
+        and compute every row."""
         X = X.to(self.device)
         n = X.shape[0]
         if n_dev is not None and n > self.PREDICT_CHUNK:
@@ -765,6 +796,7 @@ class GPUMLPRegressor:
         self._e_h1 = None
         self.fp4_scoring = _os_environ_flag("BODYWORK_MLP_FP4")
         self._w2_q4 = None
+        self.skinny_scoring = _os_environ_flag("BODYWORK_MLP_SKINNY")
         self.fp8_backward = _os.environ.get("BODYWORK_MLP_FP8_BWD",
                                             "0") == "1"
         self.fp8_training = self.fp8_backward or _os.environ.get(

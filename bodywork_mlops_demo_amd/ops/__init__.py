@@ -1373,6 +1373,45 @@ def linear_relu_dot_bf16(
     return _zero_dead_rows(h2 @ w3.float(), n_dev)
 
 
+def mlp_skinny_score(
+    x: torch.Tensor,
+    mu: float,
+    sigma: float,
+    w1: torch.Tensor,
+    b1: torch.Tensor,
+    w2: torch.Tensor,
+    b2: torch.Tensor,
+    w3: torch.Tensor,
+    b3: torch.Tensor,
+    n_dev: torch.Tensor | None = None,
+) -> torch.Tensor:
+    """The whole MLP scoring forward of 1..64 rows in ONE kernel:
+    ``y = b3 + relu(bf16(relu(xn*w1 + b1)) @ w2^T + b2) @ w3`` with ``xn =
+    (x - mu) / sigma`` (fp32 subtract and IEEE divide).
+
+    ``x`` is the raw fp32 ``[m]`` input, ``w1``/``b1`` bf16 ``[H]``, ``w2``
+    bf16 ``[H, H]`` laid out ``[out, in]``, ``b2``/``w3`` fp32 ``[H]``,
+    ``b3`` fp32 ``[1]``; ``H % 128 == 0``.  The kernel streams ``w2`` once
+    across H/16 workgroups straight into MFMA operand registers, evaluates
+    layer 1 in registers (the bits ``expand1d_bf16`` writes) and combines
+    the workgroups' partial sums in a fixed order, so the result is bitwise
+    reproducible (ops/hip/mlp_skinny.hip).
+
+    ``n_dev`` (int64[1] on x's device, clamped to [0, m]): rows at or past
+    it come out as exactly 0 and nothing in ``x[n_dev:]`` (NaN included)
+    reaches a live row.  It saves no weight traffic.  CPU oracle: fp32
+    matmul on the bf16-rounded layer 1."""
+    if x.device.type == "cuda":
+        core = _core(x.device)
+        return core.mlp_skinny_score(
+            x.contiguous().float(), float(mu), float(sigma), w1.contiguous(),
+            b1.contiguous(), w2.contiguous(), b2.contiguous(),
+            w3.contiguous(), b3.reshape(1), n_dev)
+    return _zero_dead_rows(
+        reference.mlp_skinny_score_cpu(x, mu, sigma, w1, b1, w2, b2, w3, b3),
+        n_dev)
+
+
 def transpose_bf16(src: torch.Tensor) -> torch.Tensor:
     """[C,R] bf16 = [R,C] bf16 transposed (64x64 LDS tiles, 16-B I/O)."""
     if src.device.type == "cuda":

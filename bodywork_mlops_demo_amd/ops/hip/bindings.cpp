@@ -72,6 +72,12 @@ at::Tensor rowdot_bf16_hip(const at::Tensor& h, const at::Tensor& w,
 at::Tensor coldot_bf16_hip(const at::Tensor& m, const at::Tensor& v,
                            bool also_colsum);
 at::Tensor colsum_bf16_hip(const at::Tensor& m);
+// mlp_skinny.hip
+at::Tensor mlp_skinny_score_hip(const at::Tensor& x, double mu, double sigma,
+                                const at::Tensor& w1, const at::Tensor& b1,
+                                const at::Tensor& w2, const at::Tensor& b2,
+                                const at::Tensor& w3, const at::Tensor& b3,
+                                const c10::optional<at::Tensor>& n_dev);
 // gemm.hip
 at::Tensor linear_bf16_hip(const at::Tensor& x, const at::Tensor& w,
                            const c10::optional<at::Tensor>& bias, bool relu,
@@ -182,6 +188,9 @@ TORCH_LIBRARY(bodywork_hip, m) {
   m.def("rowdot_bf16(Tensor h, Tensor w, Tensor bias) -> Tensor");
   m.def("coldot_bf16(Tensor m, Tensor v, bool also_colsum) -> Tensor");
   m.def("colsum_bf16(Tensor m) -> Tensor");
+  m.def("mlp_skinny_score(Tensor x, float mu, float sigma, Tensor w1, "
+        "Tensor b1, Tensor w2, Tensor b2, Tensor w3, Tensor b3, "
+        "Tensor? n_dev) -> Tensor");
   m.def("linear_bf16(Tensor x, Tensor w, Tensor? bias, bool relu, "
         "Tensor? mask, bool out_fp32) -> Tensor");
   m.def("linear_relu_mask_bf16(Tensor x, Tensor w, Tensor? bias) -> "
@@ -248,6 +257,7 @@ TORCH_LIBRARY_IMPL(bodywork_hip, CUDA, m) {
   m.impl("rowdot_bf16", rowdot_bf16_hip);
   m.impl("coldot_bf16", coldot_bf16_hip);
   m.impl("colsum_bf16", colsum_bf16_hip);
+  m.impl("mlp_skinny_score", mlp_skinny_score_hip);
   m.impl("linear_bf16", linear_bf16_hip);
   m.impl("linear_relu_mask_bf16", linear_relu_mask_bf16_hip);
   m.impl("gemm_tn_bf16", gemm_tn_bf16_hip);

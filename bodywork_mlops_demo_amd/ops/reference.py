@@ -453,6 +453,16 @@ def expand1d_cpu(
     return out.bfloat16()
 
 
+def mlp_skinny_score_cpu(x, mu: float, sigma: float, w1, b1, w2, b2, w3,
+                         b3) -> torch.Tensor:
+    """fp32 oracle of ``ops.mlp_skinny_score``: layer 1 rounded to bf16,
+    fp32 matmul against ``w2`` ([out, in]), relu, fp32 head."""
+    xn = (x.float() - mu) / sigma
+    h1 = expand1d_cpu(xn, w1, b1, relu=True).float()
+    h2 = torch.relu(h1 @ w2.float().t() + b2.float())
+    return h2 @ w3.float() + b3.float().reshape(())
+
+
 def rowdot_cpu(h: torch.Tensor, w: torch.Tensor, b: float = 0.0) -> torch.Tensor:
     return h.float() @ w.float() + b
 

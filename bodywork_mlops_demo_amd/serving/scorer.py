@@ -17,10 +17,15 @@ For the linear model that saves a pad fill; for the MLP it saves the
 GEMM work of the bucket's empty row tiles (the ladder's ratio is 16, so
 up to 16x): the graph keeps the bucket's grid, and every 256-row tile of
 the fused GEMM + relu + rowdot head past the count returns before it
-stages anything.  The MLP's 1- and 16-row buckets run kernels without
-tile gating and compute every row of the bucket; rows past the count
-hold whatever an earlier request left in the static input, and the
-result is sliced to the live rows as before.  The polynomial model keeps
+stages anything.  The MLP's 1- and 16-row buckets: by default they run
+the unfused kernels, which have no tile gating and compute every row of
+the bucket; rows past the count hold whatever an earlier request left in
+the static input, and the result is sliced to the live rows as before.
+With the model's ``skinny_scoring`` flag (``BODYWORK_MLP_SKINNY=1``) the
+two buckets replay the one-kernel skinny forward instead, which reads the
+count: rows past it are never read and come out as 0 (the weight stream,
+which is the cost at this size, is the same for any count).  The
+polynomial model keeps
 the pad-and-slice path.  Capture is lazy (first use of a bucket) and
 falls back to direct launches on CPU or when capture is unavailable.
 """
