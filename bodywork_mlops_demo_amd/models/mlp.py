@@ -35,6 +35,14 @@ the head in registers, instead of the five launches of the unfused path.
 It reads the persistent bf16/fp32 tensors, so a captured bucket follows a
 hot redeploy; a live row count zeroes the rows past it but saves no
 weight traffic.
+Opt-in mid scoring (``mid_scoring=True`` / ``BODYWORK_MLP_MID=1``): a batch
+of 17..256 rows (a mini-batch: the scorer's 256-row bucket) runs the whole
+forward in ONE kernel too, ``ops.mlp_mid_score``, instead of the layer-1
+expand, the 256x256-tile fused head on H/256 workgroups and the ``+ b3``.
+Same tensors and arithmetic as the skinny kernel; with a live row count it
+skips the row fragments of 16 past the count.  With both flags on, at most
+64 rows go to the skinny kernel.  A flagged 256-row batch takes this path
+ahead of the fp4/fp8/bf16 tile-gated ones.
 
 Artefact: a *real sklearn ``MLPRegressor``* with ``coefs_``/``intercepts_``
 injected, so ``joblib.load`` + ``predict`` work with stock sklearn
@@ -82,7 +90,8 @@ class GPUMLPRegressor:
                  fp8_training: bool | None = None,
                  fp8_backward: bool | None = None,
                  fp4_scoring: bool | None = None,
-                 skinny_scoring: bool | None = None):
+                 skinny_scoring: bool | None = None,
+                 mid_scoring: bool | None = None):
         self.hidden = hidden
         self.device = canonical_device(device)
         # opt-in MX-fp8 scoring forward (2x-rate K=128 scaled MFMA for the
@@ -107,6 +116,10 @@ class GPUMLPRegressor:
         if skinny_scoring is None:
             skinny_scoring = _os_environ_flag("BODYWORK_MLP_SKINNY")
         self.skinny_scoring = skinny_scoring
+        # opt-in one-kernel forward for batches of 17..256 rows
+        if mid_scoring is None:
+            mid_scoring = _os_environ_flag("BODYWORK_MLP_MID")
+        self.mid_scoring = mid_scoring
         # opt-in MX-fp8 TRAINING forward: the h2 = relu(h1 @ W2 + b2) GEMM
         # runs on e4m3 operands (with this flag alone the two backward
         # GEMMs stay bf16 and the gradients pass straight through the
@@ -331,8 +344,8 @@ class GPUMLPRegressor:
         their 1-bit activation masks (consumed by the masked backward —
         16x less mask traffic than re-reading the activations).
 
-        ``n_dev`` (scoring only; see :meth:`predict`) reaches the skinny
-        branch and the tile-gated scoring branches, whose kernels stop at
+        ``n_dev`` (scoring only; see :meth:`predict`) reaches the skinny and
+        mid branches and the tile-gated scoring branches, whose kernels stop at
         that row; every other branch ignores it and computes all rows."""
         if want_masks and n_dev is not None:
             raise ValueError("the training forward takes no live row count")
@@ -340,6 +353,13 @@ class GPUMLPRegressor:
             # the whole forward in one kernel, from raw x (the kernel
             # standardises it); never overlaps the tile-gated branches below
             yhat = ops.mlp_skinny_score(
+                x, self.X_MU, self.X_SIGMA, self.w1_bf, self.b1_bf,
+                self.W2w_bf, self.b2, self.w3, self.b3, n_dev=n_dev)
+            return yhat, None, None, None, None, None
+        if not want_masks and self._use_mid(x.shape[0]):
+            # the same for a mini-batch; takes a flagged 256-row batch ahead
+            # of the tile-gated branches below
+            yhat = ops.mlp_mid_score(
                 x, self.X_MU, self.X_SIGMA, self.w1_bf, self.b1_bf,
                 self.W2w_bf, self.b2, self.w3, self.b3, n_dev=n_dev)
             return yhat, None, None, None, None, None
@@ -411,6 +431,17 @@ class GPUMLPRegressor:
                 and 1 <= m <= self.SKINNY_MAX_ROWS
                 and self.hidden % 256 == 0)
 
+    #: largest batch of the one-kernel mini-batch forward
+    #: (ops/hip/mlp_mid.hip)
+    MID_MAX_ROWS = 256
+
+    def _use_mid(self, m: int) -> bool:
+        """One-kernel mini-batch forward: opt-in, GPU-only, 17..256 rows
+        (fewer rows are the skinny kernel's, when its flag is on)."""
+        return (self.mid_scoring and self.device.type == "cuda"
+                and 17 <= m <= self.MID_MAX_ROWS
+                and self.hidden % 256 == 0)
+
     def _use_fp8(self, m: int) -> bool:
         """MX-fp8 scoring is opt-in, GPU-only, and tile-shape-gated
         (the K=128 scaled-MFMA kernel serves M%256==0; other batch sizes
@@ -450,8 +481,10 @@ class GPUMLPRegressor:
         GPU, batches of a multiple of 256 rows skip the work past the
         count (row tiles of the fused head return at once); with
         ``skinny_scoring`` batches of at most 64 rows honour it too (rows
-        past it come out as 0); other batch sizes, and the CPU, ignore it
-        and compute every row."""
+        past it come out as 0), and with ``mid_scoring`` batches of 17..256
+        rows (rows past it come out as 0, row fragments of 16 past it are
+        skipped); other batch sizes, and the CPU, ignore it and compute
+        every row."""
         X = X.to(self.device)
         n = X.shape[0]
         if n_dev is not None and n > self.PREDICT_CHUNK:
@@ -797,6 +830,7 @@ class GPUMLPRegressor:
         self.fp4_scoring = _os_environ_flag("BODYWORK_MLP_FP4")
         self._w2_q4 = None
         self.skinny_scoring = _os_environ_flag("BODYWORK_MLP_SKINNY")
+        self.mid_scoring = _os_environ_flag("BODYWORK_MLP_MID")
         self.fp8_backward = _os.environ.get("BODYWORK_MLP_FP8_BWD",
                                             "0") == "1"
         self.fp8_training = self.fp8_backward or _os.environ.get(

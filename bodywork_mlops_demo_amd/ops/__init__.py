@@ -1412,6 +1412,45 @@ def mlp_skinny_score(
         n_dev)
 
 
+def mlp_mid_score(
+    x: torch.Tensor,
+    mu: float,
+    sigma: float,
+    w1: torch.Tensor,
+    b1: torch.Tensor,
+    w2: torch.Tensor,
+    b2: torch.Tensor,
+    w3: torch.Tensor,
+    b3: torch.Tensor,
+    n_dev: torch.Tensor | None = None,
+) -> torch.Tensor:
+    """The whole MLP scoring forward of 1..256 rows in ONE kernel: the
+    formula, operands and layouts of :func:`mlp_skinny_score` (``H % 128 ==
+    0``), for a mini-batch instead of a single request.
+
+    The kernel streams ``w2`` once across H/32 workgroups into MFMA operand
+    registers and walks the row fragments of 16 in a rolled loop, four at a
+    time, evaluating layer 1 (the bits ``expand1d_bf16`` writes) just ahead
+    of the MFMAs that consume it (ops/hip/mlp_mid.hip).  Every row is summed
+    in one fixed order, so a live row's result is bitwise reproducible and
+    independent of the batch size, the count and the other rows.
+
+    ``n_dev`` (int64[1] on x's device, clamped to [0, m]): rows at or past
+    it come out as exactly 0, nothing in ``x[n_dev:]`` (NaN included) is
+    read, and row fragments wholly past it are skipped, so the arithmetic
+    costs ``ceil(n_dev / 16)`` fragments; the weight stream is the same for
+    any count.  CPU oracle: the skinny op's."""
+    if x.device.type == "cuda":
+        core = _core(x.device)
+        return core.mlp_mid_score(
+            x.contiguous().float(), float(mu), float(sigma), w1.contiguous(),
+            b1.contiguous(), w2.contiguous(), b2.contiguous(),
+            w3.contiguous(), b3.reshape(1), n_dev)
+    return _zero_dead_rows(
+        reference.mlp_skinny_score_cpu(x, mu, sigma, w1, b1, w2, b2, w3, b3),
+        n_dev)
+
+
 def transpose_bf16(src: torch.Tensor) -> torch.Tensor:
     """[C,R] bf16 = [R,C] bf16 transposed (64x64 LDS tiles, 16-B I/O)."""
     if src.device.type == "cuda":

@@ -41,39 +41,14 @@
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 
-#include "bf16_utils.h"
-#include "expand1d.h"
 #include "host_checks.h"
 #include "live_rows.h"
 #include "mfma_tile.h"
+#include "mlp_fused.h"  // sk_a_frag, sk_combine, SK_* shared
 
-constexpr int SK_THREADS = 256;  // 4 waves
-constexpr int SK_WAVES = 4;
 constexpr int SK_COLS = 16;      // output columns of a workgroup
-constexpr int SK_CHUNK = 128;    // k of one wave step = 4 MFMAs of K=32
 constexpr int SK_AHEAD = 8;      // chunks of a wave in flight (RF = 4: half)
-constexpr int SK_SEGS = 16;      // finalise: segments of consecutive blocks
 constexpr int SK_MAX_M = 64;
-
-// layer 1 of one row at columns 8*c8 .. 8*c8+7 as an MFMA A fragment; `keep`
-// is all ones, or 0 for a dead row (an AND, so that the loads stay outside
-// any branch)
-__device__ __forceinline__ bf16x8_v sk_a_frag(float xn, unsigned int keep,
-                                              const bf16_t* __restrict__ w1,
-                                              const bf16_t* __restrict__ b1,
-                                              int c8) {
-  float h[8];
-  e1d_axpb<true, true>(xn, w1, b1, c8, h);
-  const bf16x8 packed = f32_to_bf16x8(h);
-  union {
-    bf16x8_v v;
-    unsigned int u[4];
-  } f;
-  __builtin_memcpy(&f, &packed, sizeof(f));
-#pragma unroll
-  for (int e = 0; e < 4; ++e) f.u[e] &= keep;
-  return f.v;
-}
 
 // One workgroup per CU = one wave per SIMD: the wave may use the whole
 // register file (the weight slab alone is 128 VGPRs), so the compiler is told
@@ -217,64 +192,12 @@ __attribute__((amdgpu_waves_per_eu(1, 1))) void mlp_skinny_kernel(
   }
 
   // ---- ticket: the last workgroup to arrive adds up the partials ---------
-  // Agent-scope fences (the XCDs' L2s are not coherent for plain accesses):
-  // each wave that wrote partials releases them, thread 0 releases again
-  // behind the barrier and draws; the last workgroup acquires before it
-  // reads.  Waves that wrote nothing do not fence: a fence is an L2
-  // writeback and invalidate, and 1024 waves would queue them.
-  if (wave < RF) __threadfence();
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence();
-    drawn = atomicAdd(ticket, 1u);
-  }
-  __syncthreads();
-  if (drawn != gridDim.x - 1) return;
-  __threadfence();
-
-  const int grid = (int)gridDim.x;
-  const int per = (grid + SK_SEGS - 1) / SK_SEGS;
-  float* part = &red[0][0][0];  // [RF][SK_SEGS][16]; red was last read above
-  {
-    const int seg = threadIdx.x >> 4;
-    const int r16 = threadIdx.x & 15;
-    const int g0 = seg * per;
-    const int g1 = min(g0 + per, grid);
-#pragma unroll
-    for (int r = 0; r < RF; ++r) {
-      float s = 0.0f;
-#pragma unroll 8
-      for (int g = g0; g < g1; ++g)
-        s += __hip_atomic_load(ws + (long long)g * ROWS + r * 16 + r16,
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      part[(r * SK_SEGS + seg) * 16 + r16] = s;
-    }
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < ROWS && (int)threadIdx.x < m) {
-    const int row = threadIdx.x;
-    const int r = row >> 4, r16 = row & 15;
-    float s = 0.0f;
-#pragma unroll
-    for (int seg = 0; seg < SK_SEGS; ++seg)
-      s += part[(r * SK_SEGS + seg) * 16 + r16];
-    y[row] = row < live ? s + b3[0] : 0.0f;
-  }
+  // red was last read above
+  sk_combine<RF>(wave < RF, RF, &red[0][0][0], &drawn, ws, ticket, b3, y, m,
+                 live);
 }
 
 // ---- host side --------------------------------------------------------------
-
-// a contiguous [numel] tensor of `dtype` on x's device -> its data pointer
-static const void* sk_operand(const char* op, const char* name,
-                              const at::Tensor& t, const at::Tensor& x,
-                              at::ScalarType dtype, int64_t numel) {
-  TORCH_CHECK(t.is_cuda() && t.device() == x.device() &&
-                  t.scalar_type() == dtype && t.numel() == numel &&
-                  t.is_contiguous(),
-              op, ": ", name, " must be a contiguous ", c10::toString(dtype),
-              " tensor of ", numel, " elements on x's device");
-  return t.data_ptr();
-}
 
 at::Tensor mlp_skinny_score_hip(const at::Tensor& x, double mu, double sigma,
                                 const at::Tensor& w1, const at::Tensor& b1,
@@ -282,25 +205,9 @@ at::Tensor mlp_skinny_score_hip(const at::Tensor& x, double mu, double sigma,
                                 const at::Tensor& w3, const at::Tensor& b3,
                                 const c10::optional<at::Tensor>& n_dev) {
   const char* op = "mlp_skinny_score";
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.dim() == 1 &&
-                  x.is_contiguous(),
-              op, ": x must be a contiguous 1-d fp32 cuda tensor");
-  const int64_t m = x.numel();
-  TORCH_CHECK(m >= 1 && m <= SK_MAX_M, op, ": serves 1..", SK_MAX_M,
-              " rows (got ", m, ")");
-  const int64_t H = w1.numel();
-  TORCH_CHECK(H > 0 && H % SK_CHUNK == 0 && H <= (1 << 20), op,
-              ": H must be a positive multiple of ", SK_CHUNK,
-              ", at most 2^20 (got ", H, ")");
-  TORCH_CHECK(w2.dim() == 2 && w2.size(0) == H && w2.size(1) == H, op,
-              ": w2 must be [H, H] = [out, in]");
-  const auto* w1p = (const bf16_t*)sk_operand(op, "w1", w1, x, at::kBFloat16, H);
-  const auto* b1p = (const bf16_t*)sk_operand(op, "b1", b1, x, at::kBFloat16, H);
-  const auto* w2p =
-      (const bf16_t*)sk_operand(op, "w2", w2, x, at::kBFloat16, H * H);
-  const auto* b2p = (const float*)sk_operand(op, "b2", b2, x, at::kFloat, H);
-  const auto* w3p = (const float*)sk_operand(op, "w3", w3, x, at::kFloat, H);
-  const auto* b3p = (const float*)sk_operand(op, "b3", b3, x, at::kFloat, 1);
+  const MlpScoreOperands a = mlp_score_operands(op, SK_MAX_M, SK_CHUNK, x, w1,
+                                                b1, w2, b2, w3, b3);
+  const int64_t m = a.m, H = a.H;
   const int64_t* n_live = n_live_ptr(n_dev, x, op);
 
   const int rf = m <= 16 ? 1 : (m <= 32 ? 2 : 4);
@@ -314,8 +221,9 @@ at::Tensor mlp_skinny_score_hip(const at::Tensor& x, double mu, double sigma,
 #define SK_LAUNCH(RF_)                                                       \
   hipLaunchKernelGGL((mlp_skinny_kernel<RF_>), dim3(grid), dim3(SK_THREADS), \
                      0, stream, x.data_ptr<float>(), (float)mu,              \
-                     (float)sigma, w1p, b1p, w2p, b2p, w3p, b3p, n_live,     \
-                     ws.data_ptr<float>(),                                   \
+                     (float)sigma, (const bf16_t*)a.w1,                      \
+                     (const bf16_t*)a.b1, (const bf16_t*)a.w2, a.b2, a.w3,   \
+                     a.b3, n_live, ws.data_ptr<float>(),                     \
                      (unsigned int*)ticket.data_ptr<int>(),                  \
                      y.data_ptr<float>(), (int)m, (int)H)
   if (rf == 1) SK_LAUNCH(1);

@@ -24,7 +24,12 @@ the static input, and the result is sliced to the live rows as before.
 With the model's ``skinny_scoring`` flag (``BODYWORK_MLP_SKINNY=1``) the
 two buckets replay the one-kernel skinny forward instead, which reads the
 count: rows past it are never read and come out as 0 (the weight stream,
-which is the cost at this size, is the same for any count).  The
+which is the cost at this size, is the same for any count).  With the
+model's ``mid_scoring`` flag (``BODYWORK_MLP_MID=1``) the 256-row bucket,
+which serves requests of 17..256 rows, replays the one-kernel mini-batch
+forward: it reads the count too, skips the row fragments of 16 past it and
+follows a hot redeploy like the others (no change in this module: the
+bucket already passes the count, and its warm-up runs 256 rows).  The
 polynomial model keeps
 the pad-and-slice path.  Capture is lazy (first use of a bucket) and
 falls back to direct launches on CPU or when capture is unavailable.

@@ -1,16 +1,24 @@
-"""Replay time of the MLP scorer's 1- and 16-row buckets, skinny flag on
+"""Replay time of the MLP scorer's small buckets, a one-kernel flag on
 against off, in one process.
 
-Two same-seed ``GPUMLPRegressor(hidden=H)``, one with ``skinny_scoring``,
-a ``BatchedScorer`` over each, buckets 1 and 16 captured.  Per bucket the
-two captured graphs are replayed in alternating blocks of ``--replays``
-back-to-back replays, device events around each block, ``--rounds`` times;
-per (bucket, variant) the microseconds per replay of every round are
-printed, and for the skinny path the implied weight rate ``H*H*2 bytes /
-time``.  Back-to-back replays re-read a weight matrix that fits in the
-last-level cache: a hot steady state, not a cold HBM stream.
+Two same-seed ``GPUMLPRegressor(hidden=H)``, one with ``--flag`` (``skinny``:
+``skinny_scoring``, the 1- and 16-row buckets; ``mid``: ``mid_scoring``, the
+256-row bucket), a ``BatchedScorer`` over each.  ``--cases`` lists
+``bucket:live`` pairs: the bucket is captured by a request of ``live`` rows,
+so the graph's device-side row count stays at ``live`` for the replays.
+Per case the two captured graphs are replayed in alternating blocks of
+``--replays`` back-to-back replays, device events around each block,
+``--rounds`` times; per (case, variant) the microseconds per replay of every
+round, their median and their spread are printed, and for the flagged path
+the implied weight rate ``H*H*2 bytes / time``.  Back-to-back replays re-read
+a weight matrix that fits in the last-level cache: a hot steady state, not a
+cold HBM stream.  Every (case, variant) has a model and a scorer of its own;
+the figures in profiles/skinny_scoring.md were taken with an earlier
+arrangement, one scorer per variant holding both buckets (the replayed
+graphs are the same).
 
     python tools/skinny_latency.py [--hidden 4096] [--replays 2000]
+    python tools/skinny_latency.py --flag mid [--cases 256:17,256:256]
 """
 from __future__ import annotations
 
@@ -21,14 +29,22 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+DEFAULT_CASES = {"skinny": "1:1,16:16",
+                 "mid": "256:17,256:64,256:128,256:256"}
+
 
 def main() -> None:
     p = argparse.ArgumentParser()
+    p.add_argument("--flag", choices=sorted(DEFAULT_CASES), default="skinny")
+    p.add_argument("--cases", default=None,
+                   help="bucket:live pairs, e.g. 256:17,256:256")
     p.add_argument("--hidden", type=int, default=4096)
     p.add_argument("--replays", type=int, default=2000)
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--warmup", type=int, default=200)
     args = p.parse_args()
+    cases = [tuple(int(v) for v in c.split(":"))
+             for c in (args.cases or DEFAULT_CASES[args.flag]).split(",")]
 
     import torch
 
@@ -38,35 +54,42 @@ def main() -> None:
     assert torch.cuda.is_available(), "skinny_latency needs a GPU"
     dev = "cuda:0"
     g = torch.Generator(device="cpu").manual_seed(1)
-    rows = (torch.rand(16, generator=g) * 100).to(dev)
+    rows = (torch.rand(max(b for b, _ in cases), generator=g) * 100).to(dev)
+    variants = ("unfused", args.flag)
     graphs: dict = {}
     outs: dict = {}
-    for variant, flag in (("unfused", False), ("skinny", True)):
-        model = GPUMLPRegressor(hidden=args.hidden, device=dev, seed=7,
-                                skinny_scoring=flag)
-        scorer = BatchedScorer(model, dev, use_graphs=True)
-        for b in (1, 16):
-            outs[b, variant] = scorer.score_tensor(rows[:b])
+    keep = []  # the scorers own the graphs' static buffers
+    for b, live in cases:
+        assert 1 <= live <= b, f"case {b}:{live}"
+        for variant in variants:
+            model = GPUMLPRegressor(
+                hidden=args.hidden, device=dev, seed=7,
+                **{f"{args.flag}_scoring": variant != "unfused"})
+            # one scorer per case: its bucket keeps this live count
+            scorer = BatchedScorer(model, dev, use_graphs=True)
+            outs[b, live, variant] = scorer.score_tensor(rows[:live])
             assert scorer.use_graphs, "graph capture fell back"
-            graphs[b, variant] = scorer._graphs[b][0]
-        graphs[variant] = scorer  # keeps the static buffers alive
-    for b in (1, 16):
-        d = (outs[b, "skinny"] - outs[b, "unfused"]).abs().max().item()
-        print(f"bucket {b}: max |skinny - unfused| = {d:.3e} "
-              f"(max |y| {outs[b, 'unfused'].abs().max().item():.3f})")
+            assert sorted(scorer._graphs) == [b], (b, sorted(scorer._graphs))
+            graphs[b, live, variant] = scorer._graphs[b][0]
+            keep.append(scorer)
+        ref = outs[b, live, "unfused"]
+        d = (outs[b, live, args.flag] - ref).abs().max().item()
+        print(f"bucket {b} live {live}: max |{args.flag} - unfused| = "
+              f"{d:.3e} (max |y| {ref.abs().max().item():.3f})")
 
     wbytes = args.hidden * args.hidden * 2
     start = torch.cuda.Event(enable_timing=True)
     stop = torch.cuda.Event(enable_timing=True)
-    result = {"hidden": args.hidden, "replays": args.replays}
-    for b in (1, 16):
-        us = {"unfused": [], "skinny": []}
+    result = {"hidden": args.hidden, "replays": args.replays,
+              "flag": args.flag}
+    for b, live in cases:
+        us = {variant: [] for variant in variants}
         for variant in us:
             for _ in range(args.warmup):
-                graphs[b, variant].replay()
+                graphs[b, live, variant].replay()
         for _ in range(args.rounds):
             for variant in us:
-                graph = graphs[b, variant]
+                graph = graphs[b, live, variant]
                 start.record()
                 for _ in range(args.replays):
                     graph.replay()
@@ -76,13 +99,13 @@ def main() -> None:
                     start.elapsed_time(stop) * 1e3 / args.replays)
         for variant, v in us.items():
             med = sorted(v)[len(v) // 2]
-            line = (f"bucket {b:2d} {variant:8s} us/replay by round: "
-                    + ", ".join(f"{t:.2f}" for t in v)
-                    + f"  median {med:.2f}")
-            if variant == "skinny":
+            line = (f"bucket {b:3d} live {live:3d} {variant:8s} us/replay by "
+                    "round: " + ", ".join(f"{t:.2f}" for t in v)
+                    + f"  median {med:.2f}  spread {max(v) - min(v):.2f}")
+            if variant != "unfused":
                 line += f"  weights {wbytes / med / 1e6:.2f} TB/s"
             print(line)
-            result[f"b{b}_{variant}_us"] = [round(t, 3) for t in v]
+            result[f"b{b}_n{live}_{variant}_us"] = [round(t, 3) for t in v]
     print(json.dumps(result))
 
 
