@@ -43,6 +43,15 @@ Same tensors and arithmetic as the skinny kernel; with a live row count it
 skips the row fragments of 16 past the count.  With both flags on, at most
 64 rows go to the skinny kernel.  A flagged 256-row batch takes this path
 ahead of the fp4/fp8/bf16 tile-gated ones.
+Opt-in skinny fp4 scoring (``skinny_fp4=True`` /
+``BODYWORK_MLP_SKINNY_FP4=1``): a batch of at most 64 rows runs the one-kernel
+forward on the MXFP4 shadow of ``W2`` (``ops.mlp_skinny_score_mxfp4``: the
+codes and block scales the ``fp4_scoring`` path keeps, a quarter of the bf16
+bytes; layer 1 is quantised in registers to the bits ``expand1d_mxfp4``
+writes).  Independent of ``skinny_scoring`` and ``fp4_scoring`` and taken
+ahead of the former; set it beside ``fp4_scoring`` for a model that is fp4 at
+every batch size.  The shadow is requantised in place on a hot redeploy, so a
+captured bucket follows it.
 
 Artefact: a *real sklearn ``MLPRegressor``* with ``coefs_``/``intercepts_``
 injected, so ``joblib.load`` + ``predict`` work with stock sklearn
@@ -91,7 +100,8 @@ class GPUMLPRegressor:
                  fp8_backward: bool | None = None,
                  fp4_scoring: bool | None = None,
                  skinny_scoring: bool | None = None,
-                 mid_scoring: bool | None = None):
+                 mid_scoring: bool | None = None,
+                 skinny_fp4: bool | None = None):
         self.hidden = hidden
         self.device = canonical_device(device)
         # opt-in MX-fp8 scoring forward (2x-rate K=128 scaled MFMA for the
@@ -120,6 +130,11 @@ class GPUMLPRegressor:
         if mid_scoring is None:
             mid_scoring = _os_environ_flag("BODYWORK_MLP_MID")
         self.mid_scoring = mid_scoring
+        # opt-in one-kernel forward for batches of at most 64 rows on the
+        # MXFP4 shadow of W2 (_w2_q4); independent of the flags above
+        if skinny_fp4 is None:
+            skinny_fp4 = _os_environ_flag("BODYWORK_MLP_SKINNY_FP4")
+        self.skinny_fp4 = skinny_fp4
         # opt-in MX-fp8 TRAINING forward: the h2 = relu(h1 @ W2 + b2) GEMM
         # runs on e4m3 operands (with this flag alone the two backward
         # GEMMs stay bf16 and the gradients pass straight through the
@@ -349,6 +364,14 @@ class GPUMLPRegressor:
         that row; every other branch ignores it and computes all rows."""
         if want_masks and n_dev is not None:
             raise ValueError("the training forward takes no live row count")
+        if not want_masks and self._use_skinny_fp4(x.shape[0]):
+            # the one-kernel forward on the MXFP4 shadow of W2, read as the
+            # tile-gated fp4 branch below reads it
+            self._ensure_fp4_weights()
+            yhat = ops.mlp_skinny_score_mxfp4(
+                x, self.X_MU, self.X_SIGMA, self.w1_bf, self.b1_bf,
+                *self._w2_q4, self.b2, self.w3, self.b3, n_dev=n_dev)
+            return yhat, None, None, None, None, None
         if not want_masks and self._use_skinny(x.shape[0]):
             # the whole forward in one kernel, from raw x (the kernel
             # standardises it); never overlaps the tile-gated branches below
@@ -431,6 +454,13 @@ class GPUMLPRegressor:
                 and 1 <= m <= self.SKINNY_MAX_ROWS
                 and self.hidden % 256 == 0)
 
+    def _use_skinny_fp4(self, m: int) -> bool:
+        """One-kernel skinny forward on MXFP4 weights: opt-in, GPU-only,
+        1..64 rows; taken ahead of :meth:`_use_skinny`."""
+        return (self.skinny_fp4 and self.device.type == "cuda"
+                and 1 <= m <= self.SKINNY_MAX_ROWS
+                and self.hidden % 256 == 0)
+
     #: largest batch of the one-kernel mini-batch forward
     #: (ops/hip/mlp_mid.hip)
     MID_MAX_ROWS = 256
@@ -480,8 +510,8 @@ class GPUMLPRegressor:
         ``< n_dev`` of the result are right, the rest unspecified.  On the
         GPU, batches of a multiple of 256 rows skip the work past the
         count (row tiles of the fused head return at once); with
-        ``skinny_scoring`` batches of at most 64 rows honour it too (rows
-        past it come out as 0), and with ``mid_scoring`` batches of 17..256
+        ``skinny_scoring`` or ``skinny_fp4`` batches of at most 64 rows
+        honour it too (rows past it come out as 0), and with ``mid_scoring`` batches of 17..256
         rows (rows past it come out as 0, row fragments of 16 past it are
         skipped); other batch sizes, and the CPU, ignore it and compute
         every row."""
@@ -831,6 +861,7 @@ class GPUMLPRegressor:
         self._w2_q4 = None
         self.skinny_scoring = _os_environ_flag("BODYWORK_MLP_SKINNY")
         self.mid_scoring = _os_environ_flag("BODYWORK_MLP_MID")
+        self.skinny_fp4 = _os_environ_flag("BODYWORK_MLP_SKINNY_FP4")
         self.fp8_backward = _os.environ.get("BODYWORK_MLP_FP8_BWD",
                                             "0") == "1"
         self.fp8_training = self.fp8_backward or _os.environ.get(

@@ -1412,6 +1412,43 @@ def mlp_skinny_score(
         n_dev)
 
 
+def mlp_skinny_score_mxfp4(
+    x: torch.Tensor,
+    mu: float,
+    sigma: float,
+    w1: torch.Tensor,
+    b1: torch.Tensor,
+    w2q: torch.Tensor,
+    w2s: torch.Tensor,
+    b2: torch.Tensor,
+    w3: torch.Tensor,
+    b3: torch.Tensor,
+    n_dev: torch.Tensor | None = None,
+) -> torch.Tensor:
+    """:func:`mlp_skinny_score` on MXFP4 operands, 1..64 rows in ONE kernel:
+    ``y = b3 + relu(dq(h1) @ dq(w2)^T + b2) @ w3`` with ``h1 = relu(xn*w1 +
+    b1)`` in fp32 and ``xn = (x - mu) / sigma``.
+
+    ``w2q``/``w2s`` are ``quantize_mxfp4`` of the ``[out, in]`` matrix
+    (codes ``[H, H/2]``, scales ``[H*H/32]``), read as they are: a quarter
+    of the bf16 bytes.  ``h1`` is quantised in registers to the codes and
+    block scales ``expand1d_mxfp4`` writes for the same ``xn`` and never
+    stored; the fp4 scaled MFMA (K = 128) multiplies, fp32 accumulates
+    (ops/hip/mlp_skinny_mx4.hip).  The other operands, ``n_dev`` and the
+    fixed-order, bitwise reproducible combine are the bf16 op's; ``H % 256
+    == 0``.  CPU oracle: ``reference.mlp_skinny_score_mxfp4_cpu``."""
+    if x.device.type == "cuda":
+        core = _core(x.device)
+        return core.mlp_skinny_score_mxfp4(
+            x.contiguous().float(), float(mu), float(sigma), w1.contiguous(),
+            b1.contiguous(), w2q.contiguous(), w2s.contiguous(),
+            b2.contiguous(), w3.contiguous(), b3.reshape(1), n_dev)
+    return _zero_dead_rows(
+        reference.mlp_skinny_score_mxfp4_cpu(x, mu, sigma, w1, b1, w2q, w2s,
+                                             b2, w3, b3),
+        n_dev)
+
+
 def mlp_mid_score(
     x: torch.Tensor,
     mu: float,

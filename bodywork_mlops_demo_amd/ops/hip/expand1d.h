@@ -144,24 +144,24 @@ __device__ __forceinline__ int mx4_block_exponent(unsigned int amax_bits) {
   return min(max(e, -127), 127);
 }
 
-// 8 values of one thread -> 8 e2m1 codes (one 4-byte store, element 2i in the
-// low nibble of byte i) and, from the first of the four ADJACENT lanes that
-// hold a 32-block, its E8M0 byte.  The block amax is two cross-lane steps
-// over the |value| bit patterns (monotone as unsigned ints; NaN and inf sort
-// on top).  Every lane of such a group of four must be active: callers
-// iterate (row, c8) with c8 fastest and H/8 a multiple of 4.  Values are
-// scaled exactly (ldexpf) and converted at unit scale by the packed RNE
-// convert, which saturates at +-6.
-__device__ __forceinline__ void e1d_store_mxfp4(
-    unsigned char* __restrict__ q, unsigned char* __restrict__ s,
-    long long row, int h8, int c8, const float (&acc)[8]) {
+// The quantiser's arithmetic on 8 values of one thread, shared by
+// e1d_store_mxfp4 below and by the skinny fp4 forward (mlp_skinny_mx4.hip),
+// which quantises in registers: what both emit is the same bits by
+// construction.  mx4_amax8: the largest |value| bit pattern (monotone as
+// unsigned ints; NaN and inf sort on top).  mx4_pack8: the 8 e2m1 codes at
+// block exponent e, element 2i in the low nibble of byte i; values are scaled
+// exactly (ldexpf) and converted at unit scale by the packed RNE convert,
+// which saturates at +-6.
+__device__ __forceinline__ unsigned int mx4_amax8(const float (&acc)[8]) {
   unsigned int am = 0u;
 #pragma unroll
   for (int e = 0; e < 8; ++e)
     am = max(am, __float_as_uint(acc[e]) & 0x7FFFFFFFu);
-  am = max(am, (unsigned int)__shfl_xor((int)am, 1, 64));
-  am = max(am, (unsigned int)__shfl_xor((int)am, 2, 64));
-  const int e = mx4_block_exponent(am);
+  return am;
+}
+
+__device__ __forceinline__ unsigned int mx4_pack8(const float (&acc)[8],
+                                                  int e) {
   float v[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) v[k] = ldexpf(acc[k], -e);
@@ -170,6 +170,23 @@ __device__ __forceinline__ void e1d_store_mxfp4(
   pk = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(pk, v[2], v[3], 1.0f, 1);
   pk = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(pk, v[4], v[5], 1.0f, 2);
   pk = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(pk, v[6], v[7], 1.0f, 3);
+  return pk;
+}
+
+// 8 values of one thread -> 8 e2m1 codes (one 4-byte store, element 2i in the
+// low nibble of byte i) and, from the first of the four ADJACENT lanes that
+// hold a 32-block, its E8M0 byte.  The block amax is two cross-lane steps
+// over the four lanes' mx4_amax8.  Every lane of such a group of four must
+// be active: callers iterate (row, c8) with c8 fastest and H/8 a multiple of
+// 4.
+__device__ __forceinline__ void e1d_store_mxfp4(
+    unsigned char* __restrict__ q, unsigned char* __restrict__ s,
+    long long row, int h8, int c8, const float (&acc)[8]) {
+  unsigned int am = mx4_amax8(acc);
+  am = max(am, (unsigned int)__shfl_xor((int)am, 1, 64));
+  am = max(am, (unsigned int)__shfl_xor((int)am, 2, 64));
+  const int e = mx4_block_exponent(am);
+  const unsigned int pk = mx4_pack8(acc, e);
   *(unsigned int*)(q + ((row * h8 + c8) << 2)) = pk;
   if ((c8 & 3) == 0)
     s[mx4_scale_index(row, c8 >> 2, h8 >> 5)] = (unsigned char)(e + 127);

@@ -30,18 +30,20 @@ static inline const void* mlp_score_operand(const char* op, const char* name,
   return t.data_ptr();
 }
 
-// what both host entries check alike: x fp32 [1..max_m], H = w1.numel() a
-// multiple of k_chunk; w1, b1, w2 are bf16
+// what the host entries check alike: x fp32 [1..max_m], H = w1.numel() a
+// multiple of k_chunk; w1, b1 (and a bf16 w2) are bf16
 struct MlpScoreOperands {
   int64_t m = 0, H = 0;
   const void *w1 = nullptr, *b1 = nullptr, *w2 = nullptr;
   const float *b2 = nullptr, *w3 = nullptr, *b3 = nullptr;
 };
 
-static inline MlpScoreOperands mlp_score_operands(
+// everything but w2, whose format is the kernel's (mlp_skinny_mx4.hip takes
+// MXFP4 codes and scales)
+static inline MlpScoreOperands mlp_score_vectors(
     const char* op, int64_t max_m, int64_t k_chunk, const at::Tensor& x,
-    const at::Tensor& w1, const at::Tensor& b1, const at::Tensor& w2,
-    const at::Tensor& b2, const at::Tensor& w3, const at::Tensor& b3) {
+    const at::Tensor& w1, const at::Tensor& b1, const at::Tensor& b2,
+    const at::Tensor& w3, const at::Tensor& b3) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.dim() == 1 &&
                   x.is_contiguous(),
               op, ": x must be a contiguous 1-d fp32 cuda tensor");
@@ -53,13 +55,22 @@ static inline MlpScoreOperands mlp_score_operands(
   TORCH_CHECK(H > 0 && H % k_chunk == 0 && H <= (1 << 20), op,
               ": H must be a positive multiple of ", k_chunk,
               ", at most 2^20 (got ", H, ")");
-  TORCH_CHECK(w2.dim() == 2 && w2.size(0) == H && w2.size(1) == H, op,
-              ": w2 must be [H, H] = [out, in]");
   a.w1 = mlp_score_operand(op, "w1", w1, x, at::kBFloat16, H);
   a.b1 = mlp_score_operand(op, "b1", b1, x, at::kBFloat16, H);
-  a.w2 = mlp_score_operand(op, "w2", w2, x, at::kBFloat16, H * H);
   a.b2 = (const float*)mlp_score_operand(op, "b2", b2, x, at::kFloat, H);
   a.w3 = (const float*)mlp_score_operand(op, "w3", w3, x, at::kFloat, H);
   a.b3 = (const float*)mlp_score_operand(op, "b3", b3, x, at::kFloat, 1);
+  return a;
+}
+
+static inline MlpScoreOperands mlp_score_operands(
+    const char* op, int64_t max_m, int64_t k_chunk, const at::Tensor& x,
+    const at::Tensor& w1, const at::Tensor& b1, const at::Tensor& w2,
+    const at::Tensor& b2, const at::Tensor& w3, const at::Tensor& b3) {
+  MlpScoreOperands a =
+      mlp_score_vectors(op, max_m, k_chunk, x, w1, b1, b2, w3, b3);
+  TORCH_CHECK(w2.dim() == 2 && w2.size(0) == a.H && w2.size(1) == a.H, op,
+              ": w2 must be [H, H] = [out, in]");
+  a.w2 = mlp_score_operand(op, "w2", w2, x, at::kBFloat16, a.H * a.H);
   return a;
 }

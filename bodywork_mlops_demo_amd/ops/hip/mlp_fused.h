@@ -1,9 +1,9 @@
-// What the one-kernel MLP scoring forwards (mlp_skinny.hip: 1..64 rows,
-// mlp_mid.hip: 1..256 rows) share: the layer-1 MFMA A fragment, the combine
-// of the workgroups' partial sums behind an integer ticket (their host
-// entries share mlp_score_operands, host_checks.h).  Both kernels run 4
-// waves, split K over them in 128-wide chunks and write one fp32 partial per
-// row and workgroup.
+// What the one-kernel MLP scoring forwards (mlp_skinny.hip and its MXFP4
+// twin mlp_skinny_mx4.hip: 1..64 rows, mlp_mid.hip: 1..256 rows) share: the
+// bf16 layer-1 MFMA A fragment, the skinny head, the combine of the
+// workgroups' partial sums behind an integer ticket (their host entries share
+// the checks of host_checks.h).  All of them run 4 waves, split K over them
+// in 128-wide chunks and write one fp32 partial per row and workgroup.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,6 +33,49 @@ __device__ __forceinline__ bf16x8_v sk_a_frag(float xn, unsigned int keep,
 #pragma unroll
   for (int e = 0; e < 4; ++e) f.u[e] &= keep;
   return f.v;
+}
+
+// The skinny kernels' head: the four waves' accumulators of a workgroup's 16
+// columns n0.. are added through LDS in wave order, then +b2, relu, *w3 and a
+// butterfly over the 16 columns; one fp32 partial per row goes to
+// ws[blockIdx.x][16*RF].  mlp_skinny_mx4.hip calls it; mlp_skinny.hip writes
+// the same statements out in its kernel (built on this function its register
+// allocation changes throughout, and that kernel is the measured baseline of
+// profiles/skinny_scoring.md, so it is left as it was).  `red` is LDS for
+// SK_WAVES * RF*4 * 64 floats, [wave][fragment*4 + reg][lane].  Call it with
+// the whole block.  C layout: lane (fl, kg), reg q = row kg*4 + q of the
+// fragment, column fl.
+template <int RF, class Acc>
+__device__ __forceinline__ void sk_head(const Acc (&acc)[RF], float* red,
+                                        const float* __restrict__ b2,
+                                        const float* __restrict__ w3,
+                                        float* __restrict__ ws, int n0,
+                                        int wave, int lane) {
+  constexpr int ROWS = 16 * RF;
+  const int fl = lane & 15;
+  const int kg = lane >> 4;
+#pragma unroll
+  for (int r = 0; r < RF; ++r)
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      red[((wave * RF + r) * 4 + q) * 64 + lane] = acc[r][q];
+  __syncthreads();
+  for (int r = wave; r < RF; r += SK_WAVES) {
+    const float b2v = b2[n0 + fl];
+    const float w3v = w3[n0 + fl];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float v = red[(r * 4 + q) * 64 + lane];
+#pragma unroll
+      for (int w = 1; w < SK_WAVES; ++w)
+        v += red[((w * RF + r) * 4 + q) * 64 + lane];
+      float t = fmaxf(v + b2v, 0.0f) * w3v;
+#pragma unroll
+      for (int s = 1; s < 16; s <<= 1) t += __shfl_xor(t, s, 64);
+      if (fl == 0)
+        ws[(long long)blockIdx.x * ROWS + r * 16 + kg * 4 + q] = t;
+    }
+  }
 }
 
 // The last workgroup to arrive adds up the partials ws[grid][16*RF] of row

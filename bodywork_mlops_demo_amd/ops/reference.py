@@ -782,3 +782,22 @@ def gemm_mxfp4_nt_cpu(aq, sa, bq, sb, bias=None, relu=False,
     if relu:
         c = torch.relu(c)
     return c if out_fp32 else c.to(torch.bfloat16)
+
+
+def mlp_skinny_score_mxfp4_cpu(x, mu: float, sigma: float, w1, b1, w2q, w2s,
+                               b2, w3, b3) -> torch.Tensor:
+    """fp32 oracle of ``ops.mlp_skinny_score_mxfp4``: layer 1 in fp32,
+    quantised by :func:`quantize_mxfp4_cpu` (rows padded to 64, the scale
+    layout's row group), both operands decoded, fp32 matmul against the
+    ``[out, in]`` weights, relu, fp32 head."""
+    xn = (x.detach().cpu().float() - mu) / sigma
+    m, H = xn.shape[0], w1.numel()
+    h1 = torch.zeros(64, H)
+    # + 0.0: relu keeps a negative zero, whose sign would reach the code
+    h1[:m] = torch.relu(torch.outer(xn, w1.detach().cpu().float())
+                        + b1.detach().cpu().float()) + 0.0
+    h1 = mxfp4_decode_cpu(*quantize_mxfp4_cpu(h1), H)[:m]
+    w2 = mxfp4_decode_cpu(w2q, w2s, H)
+    h2 = torch.relu(h1 @ w2.t() + b2.detach().cpu().float())
+    return h2 @ w3.detach().cpu().float() \
+        + b3.detach().cpu().float().reshape(())

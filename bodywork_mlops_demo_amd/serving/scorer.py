@@ -29,7 +29,12 @@ model's ``mid_scoring`` flag (``BODYWORK_MLP_MID=1``) the 256-row bucket,
 which serves requests of 17..256 rows, replays the one-kernel mini-batch
 forward: it reads the count too, skips the row fragments of 16 past it and
 follows a hot redeploy like the others (no change in this module: the
-bucket already passes the count, and its warm-up runs 256 rows).  The
+bucket already passes the count, and its warm-up runs 256 rows).  With
+the model's ``skinny_fp4`` flag (``BODYWORK_MLP_SKINNY_FP4=1``) the 1- and
+16-row buckets replay the one-kernel forward on the MXFP4 shadow of W2
+instead (same count contract).  The shadow is quantised by the bucket's
+warm-up forwards, before capture, and requantised in place by
+``update_model``, so the captured buckets follow a hot redeploy.  The
 polynomial model keeps
 the pad-and-slice path.  Capture is lazy (first use of a bucket) and
 falls back to direct launches on CPU or when capture is unavailable.

@@ -29,6 +29,7 @@ sources = [
     os.path.join(HIP_DIR, "resid_select_binned.hip"),
     os.path.join(HIP_DIR, "mlp_small.hip"),
     os.path.join(HIP_DIR, "mlp_skinny.hip"),
+    os.path.join(HIP_DIR, "mlp_skinny_mx4.hip"),
     os.path.join(HIP_DIR, "mlp_mid.hip"),
     os.path.join(HIP_DIR, "gemm.hip"),
     os.path.join(HIP_DIR, "gemm8.hip"),

@@ -3,14 +3,17 @@ against off, in one process.
 
 Two same-seed ``GPUMLPRegressor(hidden=H)``, one with ``--flag`` (``skinny``:
 ``skinny_scoring``, the 1- and 16-row buckets; ``mid``: ``mid_scoring``, the
-256-row bucket), a ``BatchedScorer`` over each.  ``--cases`` lists
+256-row bucket; ``skinny_fp4``: ``skinny_fp4``, the same two buckets on the
+MXFP4 weights, timed against the bf16 ``skinny`` variant instead of the
+unfused path), a ``BatchedScorer`` over each.  ``--cases`` lists
 ``bucket:live`` pairs: the bucket is captured by a request of ``live`` rows,
 so the graph's device-side row count stays at ``live`` for the replays.
 Per case the two captured graphs are replayed in alternating blocks of
 ``--replays`` back-to-back replays, device events around each block,
 ``--rounds`` times; per (case, variant) the microseconds per replay of every
 round, their median and their spread are printed, and for the flagged path
-the implied weight rate ``H*H*2 bytes / time``.  Back-to-back replays re-read
+the implied weight rate, ``H*H*2`` bytes (MXFP4: ``H*H*17/32``) over the
+time.  Back-to-back replays re-read
 a weight matrix that fits in the last-level cache: a hot steady state, not a
 cold HBM stream.  Every (case, variant) has a model and a scorer of its own;
 the figures in profiles/skinny_scoring.md were taken with an earlier
@@ -19,6 +22,7 @@ graphs are the same).
 
     python tools/skinny_latency.py [--hidden 4096] [--replays 2000]
     python tools/skinny_latency.py --flag mid [--cases 256:17,256:256]
+    python tools/skinny_latency.py --flag skinny_fp4
 """
 from __future__ import annotations
 
@@ -30,7 +34,15 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 DEFAULT_CASES = {"skinny": "1:1,16:16",
-                 "mid": "256:17,256:64,256:128,256:256"}
+                 "mid": "256:17,256:64,256:128,256:256",
+                 "skinny_fp4": "1:1,16:16"}
+#: variant -> the model flags it sets, and the bytes of W2 it streams per H*H
+VARIANTS = {"unfused": ({}, None),
+            "skinny": ({"skinny_scoring": True}, 2.0),
+            "mid": ({"mid_scoring": True}, 2.0),
+            "skinny_fp4": ({"skinny_fp4": True}, 17 / 32)}
+#: what a flag is timed against
+BASELINE = {"skinny": "unfused", "mid": "unfused", "skinny_fp4": "skinny"}
 
 
 def main() -> None:
@@ -55,16 +67,16 @@ def main() -> None:
     dev = "cuda:0"
     g = torch.Generator(device="cpu").manual_seed(1)
     rows = (torch.rand(max(b for b, _ in cases), generator=g) * 100).to(dev)
-    variants = ("unfused", args.flag)
+    base = BASELINE[args.flag]
+    variants = (base, args.flag)
     graphs: dict = {}
     outs: dict = {}
     keep = []  # the scorers own the graphs' static buffers
     for b, live in cases:
         assert 1 <= live <= b, f"case {b}:{live}"
         for variant in variants:
-            model = GPUMLPRegressor(
-                hidden=args.hidden, device=dev, seed=7,
-                **{f"{args.flag}_scoring": variant != "unfused"})
+            model = GPUMLPRegressor(hidden=args.hidden, device=dev, seed=7,
+                                    **VARIANTS[variant][0])
             # one scorer per case: its bucket keeps this live count
             scorer = BatchedScorer(model, dev, use_graphs=True)
             outs[b, live, variant] = scorer.score_tensor(rows[:live])
@@ -72,12 +84,11 @@ def main() -> None:
             assert sorted(scorer._graphs) == [b], (b, sorted(scorer._graphs))
             graphs[b, live, variant] = scorer._graphs[b][0]
             keep.append(scorer)
-        ref = outs[b, live, "unfused"]
+        ref = outs[b, live, base]
         d = (outs[b, live, args.flag] - ref).abs().max().item()
-        print(f"bucket {b} live {live}: max |{args.flag} - unfused| = "
+        print(f"bucket {b} live {live}: max |{args.flag} - {base}| = "
               f"{d:.3e} (max |y| {ref.abs().max().item():.3f})")
 
-    wbytes = args.hidden * args.hidden * 2
     start = torch.cuda.Event(enable_timing=True)
     stop = torch.cuda.Event(enable_timing=True)
     result = {"hidden": args.hidden, "replays": args.replays,
@@ -99,10 +110,11 @@ def main() -> None:
                     start.elapsed_time(stop) * 1e3 / args.replays)
         for variant, v in us.items():
             med = sorted(v)[len(v) // 2]
-            line = (f"bucket {b:3d} live {live:3d} {variant:8s} us/replay by "
+            line = (f"bucket {b:3d} live {live:3d} {variant:10s} us/replay by "
                     "round: " + ", ".join(f"{t:.2f}" for t in v)
                     + f"  median {med:.2f}  spread {max(v) - min(v):.2f}")
-            if variant != "unfused":
+            if VARIANTS[variant][1]:
+                wbytes = args.hidden * args.hidden * VARIANTS[variant][1]
                 line += f"  weights {wbytes / med / 1e6:.2f} TB/s"
             print(line)
             result[f"b{b}_n{live}_{variant}_us"] = [round(t, 3) for t in v]
