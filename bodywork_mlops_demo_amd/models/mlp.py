@@ -52,6 +52,14 @@ writes).  Independent of ``skinny_scoring`` and ``fp4_scoring`` and taken
 ahead of the former; set it beside ``fp4_scoring`` for a model that is fp4 at
 every batch size.  The shadow is requantised in place on a hot redeploy, so a
 captured bucket follows it.
+Opt-in mid fp4 scoring (``mid_fp4=True`` / ``BODYWORK_MLP_MID_FP4=1``): a
+batch of 17..256 rows runs the mini-batch forward on the same shadow
+(``ops.mlp_mid_score_mxfp4``: a stage kernel quantises layer 1 once, a head
+kernel streams the codes and keeps every row fragment's accumulators in
+registers).  Independent of the other flags and taken ahead of ``mid_scoring``
+and the tile-gated branches; beside ``skinny_fp4`` and ``fp4_scoring`` it
+makes the model fp4 at every batch size, so a row's arithmetic no longer
+depends on how many rows shared its request.
 
 Artefact: a *real sklearn ``MLPRegressor``* with ``coefs_``/``intercepts_``
 injected, so ``joblib.load`` + ``predict`` work with stock sklearn
@@ -101,7 +109,8 @@ class GPUMLPRegressor:
                  fp4_scoring: bool | None = None,
                  skinny_scoring: bool | None = None,
                  mid_scoring: bool | None = None,
-                 skinny_fp4: bool | None = None):
+                 skinny_fp4: bool | None = None,
+                 mid_fp4: bool | None = None):
         self.hidden = hidden
         self.device = canonical_device(device)
         # opt-in MX-fp8 scoring forward (2x-rate K=128 scaled MFMA for the
@@ -135,6 +144,10 @@ class GPUMLPRegressor:
         if skinny_fp4 is None:
             skinny_fp4 = _os_environ_flag("BODYWORK_MLP_SKINNY_FP4")
         self.skinny_fp4 = skinny_fp4
+        # the same for batches of 17..256 rows
+        if mid_fp4 is None:
+            mid_fp4 = _os_environ_flag("BODYWORK_MLP_MID_FP4")
+        self.mid_fp4 = mid_fp4
         # opt-in MX-fp8 TRAINING forward: the h2 = relu(h1 @ W2 + b2) GEMM
         # runs on e4m3 operands (with this flag alone the two backward
         # GEMMs stay bf16 and the gradients pass straight through the
@@ -360,7 +373,7 @@ class GPUMLPRegressor:
         16x less mask traffic than re-reading the activations).
 
         ``n_dev`` (scoring only; see :meth:`predict`) reaches the skinny and
-        mid branches and the tile-gated scoring branches, whose kernels stop at
+        mid branches (bf16 and fp4) and the tile-gated scoring branches, whose kernels stop at
         that row; every other branch ignores it and computes all rows."""
         if want_masks and n_dev is not None:
             raise ValueError("the training forward takes no live row count")
@@ -369,6 +382,14 @@ class GPUMLPRegressor:
             # tile-gated fp4 branch below reads it
             self._ensure_fp4_weights()
             yhat = ops.mlp_skinny_score_mxfp4(
+                x, self.X_MU, self.X_SIGMA, self.w1_bf, self.b1_bf,
+                *self._w2_q4, self.b2, self.w3, self.b3, n_dev=n_dev)
+            return yhat, None, None, None, None, None
+        if not want_masks and self._use_mid_fp4(x.shape[0]):
+            # the mini-batch forward on the same shadow; takes a flagged
+            # batch ahead of the bf16 mid branch and the tile-gated ones
+            self._ensure_fp4_weights()
+            yhat = ops.mlp_mid_score_mxfp4(
                 x, self.X_MU, self.X_SIGMA, self.w1_bf, self.b1_bf,
                 *self._w2_q4, self.b2, self.w3, self.b3, n_dev=n_dev)
             return yhat, None, None, None, None, None
@@ -472,6 +493,14 @@ class GPUMLPRegressor:
                 and 17 <= m <= self.MID_MAX_ROWS
                 and self.hidden % 256 == 0)
 
+    def _use_mid_fp4(self, m: int) -> bool:
+        """Mini-batch forward on MXFP4 weights (ops/hip/mlp_mid_mx4.hip):
+        opt-in, GPU-only, 17..256 rows; taken ahead of :meth:`_use_mid`.
+        The upper bound is the measured one, profiles/mid_mx4_scoring.md."""
+        return (self.mid_fp4 and self.device.type == "cuda"
+                and 17 <= m <= self.MID_MAX_ROWS
+                and self.hidden % 256 == 0)
+
     def _use_fp8(self, m: int) -> bool:
         """MX-fp8 scoring is opt-in, GPU-only, and tile-shape-gated
         (the K=128 scaled-MFMA kernel serves M%256==0; other batch sizes
@@ -511,9 +540,9 @@ class GPUMLPRegressor:
         GPU, batches of a multiple of 256 rows skip the work past the
         count (row tiles of the fused head return at once); with
         ``skinny_scoring`` or ``skinny_fp4`` batches of at most 64 rows
-        honour it too (rows past it come out as 0), and with ``mid_scoring`` batches of 17..256
-        rows (rows past it come out as 0, row fragments of 16 past it are
-        skipped); other batch sizes, and the CPU, ignore it and compute
+        honour it too (rows past it come out as 0), and with ``mid_scoring``
+        or ``mid_fp4`` batches of 17..256 rows (rows past it come out as 0,
+        row fragments of 16 past it are skipped); other batch sizes, and the CPU, ignore it and compute
         every row."""
         X = X.to(self.device)
         n = X.shape[0]
@@ -862,6 +891,7 @@ class GPUMLPRegressor:
         self.skinny_scoring = _os_environ_flag("BODYWORK_MLP_SKINNY")
         self.mid_scoring = _os_environ_flag("BODYWORK_MLP_MID")
         self.skinny_fp4 = _os_environ_flag("BODYWORK_MLP_SKINNY_FP4")
+        self.mid_fp4 = _os_environ_flag("BODYWORK_MLP_MID_FP4")
         self.fp8_backward = _os.environ.get("BODYWORK_MLP_FP8_BWD",
                                             "0") == "1"
         self.fp8_training = self.fp8_backward or _os.environ.get(

@@ -1488,6 +1488,49 @@ def mlp_mid_score(
         n_dev)
 
 
+def mlp_mid_score_mxfp4(
+    x: torch.Tensor,
+    mu: float,
+    sigma: float,
+    w1: torch.Tensor,
+    b1: torch.Tensor,
+    w2q: torch.Tensor,
+    w2s: torch.Tensor,
+    b2: torch.Tensor,
+    w3: torch.Tensor,
+    b3: torch.Tensor,
+    n_dev: torch.Tensor | None = None,
+) -> torch.Tensor:
+    """:func:`mlp_skinny_score_mxfp4` for a mini-batch: 1..256 rows, the same
+    formula, operands and layouts (``H % 256 == 0``), in a PAIR of kernels
+    (ops/hip/mlp_mid_mx4.hip).
+
+    The first quantises layer 1 once (the codes and block scales
+    ``expand1d_mxfp4`` writes for the same ``xn``) into a staging buffer
+    laid out as the second one's MFMA A operand, and zeroes the combine
+    ticket.  The second streams ``w2q``/``w2s`` once across H/32 workgroups
+    into operand registers, loads the A operand from the staging buffer,
+    keeps the accumulators of all 16 row fragments in registers and ends in
+    the fixed-order combine.  Every row is summed in one fixed order, so a
+    live row's result is bitwise reproducible and independent of the batch
+    size, the count and the other rows.
+
+    ``n_dev``: the contract of :func:`mlp_mid_score`: rows at or past it
+    come out as exactly 0, nothing in ``x[n_dev:]`` is read, and row
+    fragments of 16 wholly past it are neither staged nor multiplied.  CPU
+    oracle: ``reference.mlp_skinny_score_mxfp4_cpu``."""
+    if x.device.type == "cuda":
+        core = _core(x.device)
+        return core.mlp_mid_score_mxfp4(
+            x.contiguous().float(), float(mu), float(sigma), w1.contiguous(),
+            b1.contiguous(), w2q.contiguous(), w2s.contiguous(),
+            b2.contiguous(), w3.contiguous(), b3.reshape(1), n_dev)
+    return _zero_dead_rows(
+        reference.mlp_skinny_score_mxfp4_cpu(x, mu, sigma, w1, b1, w2q, w2s,
+                                             b2, w3, b3),
+        n_dev)
+
+
 def transpose_bf16(src: torch.Tensor) -> torch.Tensor:
     """[C,R] bf16 = [R,C] bf16 transposed (64x64 LDS tiles, 16-B I/O)."""
     if src.device.type == "cuda":

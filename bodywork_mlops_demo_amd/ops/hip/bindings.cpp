@@ -90,6 +90,12 @@ at::Tensor mlp_mid_score_hip(const at::Tensor& x, double mu, double sigma,
                              const at::Tensor& w2, const at::Tensor& b2,
                              const at::Tensor& w3, const at::Tensor& b3,
                              const c10::optional<at::Tensor>& n_dev);
+// mlp_mid_mx4.hip
+at::Tensor mlp_mid_score_mxfp4_hip(
+    const at::Tensor& x, double mu, double sigma, const at::Tensor& w1,
+    const at::Tensor& b1, const at::Tensor& w2q, const at::Tensor& w2s,
+    const at::Tensor& b2, const at::Tensor& w3, const at::Tensor& b3,
+    const c10::optional<at::Tensor>& n_dev);
 // gemm.hip
 at::Tensor linear_bf16_hip(const at::Tensor& x, const at::Tensor& w,
                            const c10::optional<at::Tensor>& bias, bool relu,
@@ -209,6 +215,9 @@ TORCH_LIBRARY(bodywork_hip, m) {
   m.def("mlp_mid_score(Tensor x, float mu, float sigma, Tensor w1, "
         "Tensor b1, Tensor w2, Tensor b2, Tensor w3, Tensor b3, "
         "Tensor? n_dev) -> Tensor");
+  m.def("mlp_mid_score_mxfp4(Tensor x, float mu, float sigma, Tensor w1, "
+        "Tensor b1, Tensor w2q, Tensor w2s, Tensor b2, Tensor w3, Tensor b3, "
+        "Tensor? n_dev) -> Tensor");
   m.def("linear_bf16(Tensor x, Tensor w, Tensor? bias, bool relu, "
         "Tensor? mask, bool out_fp32) -> Tensor");
   m.def("linear_relu_mask_bf16(Tensor x, Tensor w, Tensor? bias) -> "
@@ -278,6 +287,7 @@ TORCH_LIBRARY_IMPL(bodywork_hip, CUDA, m) {
   m.impl("mlp_skinny_score", mlp_skinny_score_hip);
   m.impl("mlp_skinny_score_mxfp4", mlp_skinny_score_mxfp4_hip);
   m.impl("mlp_mid_score", mlp_mid_score_hip);
+  m.impl("mlp_mid_score_mxfp4", mlp_mid_score_mxfp4_hip);
   m.impl("linear_bf16", linear_bf16_hip);
   m.impl("linear_relu_mask_bf16", linear_relu_mask_bf16_hip);
   m.impl("gemm_tn_bf16", gemm_tn_bf16_hip);

@@ -1,6 +1,7 @@
 // What the one-kernel MLP scoring forwards (mlp_skinny.hip and its MXFP4
-// twin mlp_skinny_mx4.hip: 1..64 rows, mlp_mid.hip: 1..256 rows) share: the
-// bf16 layer-1 MFMA A fragment, the skinny head, the combine of the
+// twin mlp_skinny_mx4.hip: 1..64 rows, mlp_mid.hip and its MXFP4 twin
+// mlp_mid_mx4.hip: 1..256 rows) share: the bf16 layer-1 MFMA A fragment, the
+// quantised fp4 one, the skinny head, the combine of the
 // workgroups' partial sums behind an integer ticket (their host entries share
 // the checks of host_checks.h).  All of them run 4 waves, split K over them
 // in 128-wide chunks and write one fp32 partial per row and workgroup.
@@ -33,6 +34,40 @@ __device__ __forceinline__ bf16x8_v sk_a_frag(float xn, unsigned int keep,
 #pragma unroll
   for (int e = 0; e < 4; ++e) f.u[e] &= keep;
   return f.v;
+}
+
+// ---- the MXFP4 forwards (mlp_skinny_mx4.hip, mlp_mid_mx4.hip) ---------------
+constexpr int SX_FMT = 4;  // the scaled MFMA's cbsz / blgp value for fp4
+
+typedef __attribute__((ext_vector_type(8))) int sx_i32x8;
+typedef __attribute__((ext_vector_type(4))) int sx_i32x4;
+
+// the builtin takes 8 dwords whatever the format; fp4 reads the low four
+__device__ __forceinline__ sx_i32x8 sx_operand(sx_i32x4 v) {
+  return __builtin_shufflevector(v, v, 0, 1, 2, 3, -1, -1, -1, -1);
+}
+
+// Layer 1 of one row at the 32 columns 8*c8 .. 8*c8+31 (one MX block) as an
+// fp4 MFMA A operand: codes and the block's E8M0 byte.  `keep` is all ones,
+// or 0 for a dead row or a chunk past K: zero codes, byte 127 (an AND and a
+// select, so that the w1/b1 reads and the quantiser stay outside any branch).
+__device__ __forceinline__ sx_i32x4 sx_a_block(float xn, unsigned int keep,
+                                               const bf16_t* __restrict__ w1,
+                                               const bf16_t* __restrict__ b1,
+                                               int c8, int& scale) {
+  float h[4][8];
+  unsigned int am = 0u;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    e1d_axpb<true, true>(xn, w1, b1, c8 + j, h[j]);
+    am = max(am, mx4_amax8(h[j]));
+  }
+  const int e = mx4_block_exponent(am);
+  sx_i32x4 q;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) q[j] = (int)(mx4_pack8(h[j], e) & keep);
+  scale = 127 + (e & (int)keep);
+  return q;
 }
 
 // The skinny kernels' head: the four waves' accumulators of a workgroup's 16

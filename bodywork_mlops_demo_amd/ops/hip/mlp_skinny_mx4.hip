@@ -81,45 +81,13 @@
 #include "host_checks.h"
 #include "live_rows.h"
 #include "mfma_tile.h"
-#include "mlp_fused.h"  // sk_head, sk_combine, SK_* shared
+#include "mlp_fused.h"  // sx_a_block, sk_head, sk_combine, SK_* shared
 
 constexpr int SX_COLS = 16;   // output columns of a workgroup
 constexpr int SX_AHEAD = 8;   // chunks of a wave per K group
 constexpr int SX_GK = SK_WAVES * SX_AHEAD * SK_CHUNK;  // 4096 k per group
 constexpr int SX_MAX_M = 64;
-constexpr int SX_FMT = 4;     // the scaled MFMA's cbsz / blgp value for fp4
 constexpr int SX_TILE = 256;  // K-tile of the scale layout
-
-typedef __attribute__((ext_vector_type(8))) int sx_i32x8;
-typedef __attribute__((ext_vector_type(4))) int sx_i32x4;
-
-// the builtin takes 8 dwords whatever the format; fp4 reads the low four
-__device__ __forceinline__ sx_i32x8 sx_operand(sx_i32x4 v) {
-  return __builtin_shufflevector(v, v, 0, 1, 2, 3, -1, -1, -1, -1);
-}
-
-// Layer 1 of one row at the 32 columns 8*c8 .. 8*c8+31 (one MX block) as an
-// fp4 MFMA A operand: codes and the block's E8M0 byte.  `keep` is all ones,
-// or 0 for a dead row or a chunk past K: zero codes, byte 127 (an AND and a
-// select, so that the LDS reads and the quantiser stay outside any branch).
-__device__ __forceinline__ sx_i32x4 sx_a_block(float xn, unsigned int keep,
-                                               const bf16_t* __restrict__ w1,
-                                               const bf16_t* __restrict__ b1,
-                                               int c8, int& scale) {
-  float h[4][8];
-  unsigned int am = 0u;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    e1d_axpb<true, true>(xn, w1, b1, c8 + j, h[j]);
-    am = max(am, mx4_amax8(h[j]));
-  }
-  const int e = mx4_block_exponent(am);
-  sx_i32x4 q;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) q[j] = (int)(mx4_pack8(h[j], e) & keep);
-  scale = 127 + (e & (int)keep);
-  return q;
-}
 
 // One workgroup per CU = one wave per SIMD, as in mlp_skinny.hip: the
 // compiler is told not to trade registers for an occupancy the grid never

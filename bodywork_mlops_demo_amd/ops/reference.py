@@ -786,13 +786,14 @@ def gemm_mxfp4_nt_cpu(aq, sa, bq, sb, bias=None, relu=False,
 
 def mlp_skinny_score_mxfp4_cpu(x, mu: float, sigma: float, w1, b1, w2q, w2s,
                                b2, w3, b3) -> torch.Tensor:
-    """fp32 oracle of ``ops.mlp_skinny_score_mxfp4``: layer 1 in fp32,
-    quantised by :func:`quantize_mxfp4_cpu` (rows padded to 64, the scale
+    """fp32 oracle of ``ops.mlp_skinny_score_mxfp4`` and
+    ``ops.mlp_mid_score_mxfp4``: layer 1 in fp32, quantised by
+    :func:`quantize_mxfp4_cpu` (rows padded to a multiple of 64, the scale
     layout's row group), both operands decoded, fp32 matmul against the
     ``[out, in]`` weights, relu, fp32 head."""
     xn = (x.detach().cpu().float() - mu) / sigma
     m, H = xn.shape[0], w1.numel()
-    h1 = torch.zeros(64, H)
+    h1 = torch.zeros(-(-m // 64) * 64, H)
     # + 0.0: relu keeps a negative zero, whose sign would reach the code
     h1[:m] = torch.relu(torch.outer(xn, w1.detach().cpu().float())
                         + b1.detach().cpu().float()) + 0.0

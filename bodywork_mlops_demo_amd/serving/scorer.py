@@ -32,7 +32,10 @@ follows a hot redeploy like the others (no change in this module: the
 bucket already passes the count, and its warm-up runs 256 rows).  With
 the model's ``skinny_fp4`` flag (``BODYWORK_MLP_SKINNY_FP4=1``) the 1- and
 16-row buckets replay the one-kernel forward on the MXFP4 shadow of W2
-instead (same count contract).  The shadow is quantised by the bucket's
+instead (same count contract), and with its ``mid_fp4`` flag
+(``BODYWORK_MLP_MID_FP4=1``) the 256-row bucket replays the two-kernel
+mini-batch forward on that shadow (the count contract of ``mid_scoring``;
+again no change in this module).  The shadow is quantised by the bucket's
 warm-up forwards, before capture, and requantised in place by
 ``update_model``, so the captured buckets follow a hot redeploy.  The
 polynomial model keeps

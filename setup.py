@@ -31,6 +31,7 @@ sources = [
     os.path.join(HIP_DIR, "mlp_skinny.hip"),
     os.path.join(HIP_DIR, "mlp_skinny_mx4.hip"),
     os.path.join(HIP_DIR, "mlp_mid.hip"),
+    os.path.join(HIP_DIR, "mlp_mid_mx4.hip"),
     os.path.join(HIP_DIR, "gemm.hip"),
     os.path.join(HIP_DIR, "gemm8.hip"),
     os.path.join(HIP_DIR, "gemm_mx8.hip"),

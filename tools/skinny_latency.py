@@ -5,10 +5,13 @@ Two same-seed ``GPUMLPRegressor(hidden=H)``, one with ``--flag`` (``skinny``:
 ``skinny_scoring``, the 1- and 16-row buckets; ``mid``: ``mid_scoring``, the
 256-row bucket; ``skinny_fp4``: ``skinny_fp4``, the same two buckets on the
 MXFP4 weights, timed against the bf16 ``skinny`` variant instead of the
-unfused path), a ``BatchedScorer`` over each.  ``--cases`` lists
+unfused path; ``mid_fp4``: ``mid_fp4``, the 256-row bucket on the MXFP4
+weights, timed against both the bf16 ``mid`` variant and ``fp4_tile``, the
+``fp4_scoring`` model's tile-gated path), a ``BatchedScorer`` over each.
+``--cases`` lists
 ``bucket:live`` pairs: the bucket is captured by a request of ``live`` rows,
 so the graph's device-side row count stays at ``live`` for the replays.
-Per case the two captured graphs are replayed in alternating blocks of
+Per case the variants' captured graphs are replayed in alternating blocks of
 ``--replays`` back-to-back replays, device events around each block,
 ``--rounds`` times; per (case, variant) the microseconds per replay of every
 round, their median and their spread are printed, and for the flagged path
@@ -23,6 +26,7 @@ graphs are the same).
     python tools/skinny_latency.py [--hidden 4096] [--replays 2000]
     python tools/skinny_latency.py --flag mid [--cases 256:17,256:256]
     python tools/skinny_latency.py --flag skinny_fp4
+    python tools/skinny_latency.py --flag mid_fp4
 """
 from __future__ import annotations
 
@@ -35,14 +39,18 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 DEFAULT_CASES = {"skinny": "1:1,16:16",
                  "mid": "256:17,256:64,256:128,256:256",
-                 "skinny_fp4": "1:1,16:16"}
+                 "skinny_fp4": "1:1,16:16",
+                 "mid_fp4": "256:17,256:64,256:128,256:256"}
 #: variant -> the model flags it sets, and the bytes of W2 it streams per H*H
 VARIANTS = {"unfused": ({}, None),
             "skinny": ({"skinny_scoring": True}, 2.0),
             "mid": ({"mid_scoring": True}, 2.0),
-            "skinny_fp4": ({"skinny_fp4": True}, 17 / 32)}
-#: what a flag is timed against
-BASELINE = {"skinny": "unfused", "mid": "unfused", "skinny_fp4": "skinny"}
+            "skinny_fp4": ({"skinny_fp4": True}, 17 / 32),
+            "fp4_tile": ({"fp4_scoring": True}, None),
+            "mid_fp4": ({"mid_fp4": True}, 17 / 32)}
+#: what a flag is timed against (and its results compared with)
+BASELINE = {"skinny": ("unfused",), "mid": ("unfused",),
+            "skinny_fp4": ("skinny",), "mid_fp4": ("mid", "fp4_tile")}
 
 
 def main() -> None:
@@ -67,8 +75,7 @@ def main() -> None:
     dev = "cuda:0"
     g = torch.Generator(device="cpu").manual_seed(1)
     rows = (torch.rand(max(b for b, _ in cases), generator=g) * 100).to(dev)
-    base = BASELINE[args.flag]
-    variants = (base, args.flag)
+    variants = BASELINE[args.flag] + (args.flag,)
     graphs: dict = {}
     outs: dict = {}
     keep = []  # the scorers own the graphs' static buffers
@@ -84,10 +91,11 @@ def main() -> None:
             assert sorted(scorer._graphs) == [b], (b, sorted(scorer._graphs))
             graphs[b, live, variant] = scorer._graphs[b][0]
             keep.append(scorer)
-        ref = outs[b, live, base]
-        d = (outs[b, live, args.flag] - ref).abs().max().item()
-        print(f"bucket {b} live {live}: max |{args.flag} - {base}| = "
-              f"{d:.3e} (max |y| {ref.abs().max().item():.3f})")
+        for base in BASELINE[args.flag]:
+            ref = outs[b, live, base]
+            d = (outs[b, live, args.flag] - ref).abs().max().item()
+            print(f"bucket {b} live {live}: max |{args.flag} - {base}| = "
+                  f"{d:.3e} (max |y| {ref.abs().max().item():.3f})")
 
     start = torch.cuda.Event(enable_timing=True)
     stop = torch.cuda.Event(enable_timing=True)
